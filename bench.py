@@ -14,10 +14,15 @@ the default) or a contiguous block of --total-jobs N (strong scaling: C4 = 1024 
 jobs are all-gathered over RCCL (the only collective of the path) and, after the
 timed region, checked against every rank's own results.
 
-Rank 0 prints ONE JSON line with the metric, a roofline block for the dominant kernel (HIP events
-on the library's stream over the timed region) and a cpu_baseline block (the CPU oracle restating
-the reference path, timed on a bounded sample of the same jobs at N=1), plus the pose RMSE of the
-GPU path against that CPU reference on the sample.
+Rank 0 prints ONE JSON line.  A plain run (`--gpus 1 --steps N --warmup W`) does only what the
+headline needs: it stages the inputs, warms up, times the N steps (no per-dispatch timing) and
+prints the metric with ms_per_step; `--dump-outputs DIR` also writes what the last timed step
+computed (the arrays of fbr_batch_results) as DIR/<name>.npy.  `--full` adds everything else: a
+roofline block for the dominant kernel (HIP events on the library's stream over the timed region,
+after one untimed profiled step), the STREAM-copy rate, the single-stream latency, ingest and
+exact-voxel-order lines, and a cpu_baseline block (the CPU oracle restating the reference path,
+timed on a bounded sample of the same jobs at N=1) with the pose RMSE, parity and feature-mask
+checks of the GPU path against that CPU reference on the sample.
 """
 import argparse
 import json
@@ -131,6 +136,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the untimed profiled step and the per-kernel roofline block, the "
+                         "STREAM-copy rate, the latency / ingest / exact-voxel-order lines, the CPU baselines and the "
+                         "parity and feature-mask checks against the CPU oracle (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's results (fbr_batch_results: the poses, and every "
+                         "statistics field as float64) to DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=1024, help="jobs per GPU per step (weak scaling)")
     ap.add_argument("--total-jobs", type=int, default=0,
                     help="strong scaling: N jobs per step split into contiguous per-rank blocks (C4: 1024)")
@@ -167,16 +179,33 @@ def parse():
                     help="enable the IMU deskew path (SURVEY 8f row 3): one imuDeskewInfo table per job")
     ap.add_argument("--dist", action="store_true",
                     help="use the torch.distributed (RCCL) path even at world size 1 (tests)")
-    ap.add_argument("--profile", default="all", choices=["all", "dominant", "off"],
+    ap.add_argument("--profile", default=None, choices=["all", "dominant", "off"],
                     help="kernel timing inside the timed region (dispatch start/end timestamps through HIP "
-                         "events): every kernel (default), only the roofline kernel, or none")
+                         "events): every kernel (the default with --full), only the roofline kernel (needs --full: "
+                         "the untimed profiled step finds it), or none (the default without --full)")
     ap.add_argument("--pmc-json", default=os.path.join(REPO, "profiles", "hbm_traffic.json"),
                     help="per-launch HBM bytes of the dominant kernel from rocprofv3 PMC passes")
     ap.add_argument("--sq-json", default=os.path.join(REPO, "profiles", "sq_decomp.json"),
                     help="per-kernel wave-state / instruction-mix decomposition (tools/sq_decomp.py)")
     ap.add_argument("--valu-json", default=os.path.join(REPO, "profiles", "valu_pmc.json"),
                     help="per-launch VALU instructions of every kernel from a rocprofv3 SQ pass (tools/valu_pmc.py)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.profile is None:
+        args.profile = "all" if args.full else "off"
+    if args.profile == "dominant" and not args.full:
+        ap.error("--profile dominant needs --full")
+    return args
+
+
+def dump_outputs(out_dir, poses, stats):
+    """What a caller of the timed path receives (fbr_batch_results of the last timed step), one
+    array per file: poses.npy float32 [jobs, 6], stats_<field>.npy float64 [jobs]."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "poses.npy"), np.ascontiguousarray(poses, np.float32))
+    for f in stats.dtype.names:
+        np.save(os.path.join(out_dir, f"stats_{f}.npy"), stats[f].astype(np.float64))
 
 
 def ingest_line(ctx, scans, guesses, resident_poses, reps, B):
@@ -369,7 +398,8 @@ def main():
     guesses = np.stack([j[1] for j in jobs]).astype(np.float32)
     gts = np.stack([j[2] for j in jobs])
 
-    stream_gbps = api.stream_copy_bandwidth(dev) if rank == 0 else None  # achievable HBM copy rate
+    full = args.full
+    stream_gbps = api.stream_copy_bandwidth(dev) if full and rank == 0 else None  # achievable HBM copy rate
     ctx = api.Context(P, device=dev)
     ctx.set_map(corner_map, surf_map)
     if args.deskew:  # per-job IMU tables: 200 Hz queue around each job's scan time
@@ -446,16 +476,17 @@ def main():
     ctx.batch_wait()
     kernels = ["gn_knn", "gn_residual", "gn_solve", "project", "extract", "features", "voxel_ring", "concat",
                "voxel_scan", "gn_init", "crop", "gn_finalize", "gn_loop"]
-    # one untimed profiled step: per-kernel device times (HIP events) and the dominant kernel
-    ctx.set_profiling(True)
-    step()
-    if dist is not None and (native or args.backend == "nccl"):
-        gather_rest()
-    ctx.batch_wait()
-    ctx.set_profiling(False)
-    prof = {k: ctx.kernel_time(k) for k in kernels}
     modelled = [k for k in kernels if kernel_bytes(k, dict.fromkeys(["n_in", "HW", "n", "C", "S", "F", "Q", "IQ", "IQc"], 1.0)) > 0]
-    dom = max(modelled, key=lambda k: prof[k][0])  # the roofline kernel: the profiled step's largest
+    if full:
+        # one untimed profiled step: per-kernel device times (HIP events) and the dominant kernel
+        ctx.set_profiling(True)
+        step()
+        if dist is not None and (native or args.backend == "nccl"):
+            gather_rest()
+        ctx.batch_wait()
+        ctx.set_profiling(False)
+        prof = {k: ctx.kernel_time(k) for k in kernels}
+        dom = max(modelled, key=lambda k: prof[k][0])  # the roofline kernel: the profiled step's largest
     if dist is not None:
         import torch
         torch.cuda.synchronize()
@@ -497,8 +528,9 @@ def main():
 
     poses, stats = ctx.batch_results()
     tb, tg = ctx.batch_bytes()
-    ktot = {k: ctx.kernel_time(k) for k in kernels}
-    timed = {k: (ktot[k][0] - prof[k][0], ktot[k][1] - prof[k][1]) for k in kernels}  # timed region only
+    if full:
+        ktot = {k: ctx.kernel_time(k) for k in kernels}
+        timed = {k: (ktot[k][0] - prof[k][0], ktot[k][1] - prof[k][1]) for k in kernels}  # timed region only
     # the roofline kernel stays the profiled step's largest (dom above): in the timed region three
     # launches overlap, and a long-lived low-occupancy kernel (the mapping DS, one 1024-thread
     # workgroup per CU) accumulates as much live time as the kNN while costing the step a third of
@@ -523,6 +555,61 @@ def main():
                IQ=float(((stats["n_corner_ds"] + stats["n_surf_ds"]) * stats["iterations"]).sum()),
                IQc=float((stats["n_corner_ds"] * stats["iterations"]).sum()),
                M=float((stats["n_corner_map"] + stats["n_surf_map"]).sum()))
+
+    # pose accuracy vs ground truth (sanity) and vs the CPU reference path (metric)
+    err_gt = np.abs(poses[:, 3:] - gts[:, 3:].astype(np.float32)).max()
+    result = {
+        "metric": METRIC,
+        "value": round(value, 3),
+        "unit": "scans/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "strong" if args.total_jobs else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{cfg}: {H}x{W} {WORKLOAD[cfg]}; " + (
+                f"{args.total_jobs} independent scan-to-map jobs per step split over {world} GPU(s) (C4)"
+                if args.total_jobs else f"{B} independent scan-to-map jobs per GPU per step (C4-style independent jobs)"),
+            "jobs_per_step": int(sum(counts)),
+            "jobs_per_gpu_per_step": B,
+            "mean_points_per_scan": round(tot["n_in"] / B, 1),
+            "mean_local_map_points": round(tot["M"] / B, 1),
+            "mean_queries_per_scan": round(tot["Q"] / B, 1),
+            "mean_gn_iterations": round(float(stats["iterations"].mean()), 3),
+            "parallelism": (f"scan-shard x{world}, " + ("RCCL pose all-gather through the C-ABI (fbr_batch_allgather)"
+                                                         if native else f"{'RCCL' if args.backend == 'nccl' else 'gloo'} "
+                                                                        "pose all-gather (torch.distributed)")
+                            if dist is not None else "single GPU"),
+            "imu_deskew": bool(args.deskew),
+            "exact_voxel_order": int(args.exact_voxel_order),
+            "timed_region": ("fbr_batch_launch of a staged batch, every stage on the device: projection, features, "
+                             "per-ring and mapping VoxelGrids, CropBox statistics, Gauss-Newton registration, "
+                             "results; excludes the host-to-device copy of the raw scans and guesses "
+                             "(fbr_batch_stage: inputs resident in HBM as 16-B x, y, z, ring records packed "
+                             "by host threads, as the ingest path's records are), reported separately as "
+                             "the ingest line"),
+        },
+        "path_bytes_per_step": tb,
+        "path_achieved_GBps": round(tb / (elapsed / args.steps) / 1e9, 2),
+        "path_frac_of_peak": round(tb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
+        "max_abs_trans_err_vs_gt_m": float(err_gt),
+        "registration_status_ok": int((stats["status"] == 0).sum()),
+    }
+    if records_check is not None:
+        result["records_check"] = records_check
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, poses, stats)
+    if not full:  # the plain run ends here: the headline, its workload and the path-level figures
+        print(json.dumps(result), flush=True)
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # per-launch VALU instructions (rocprofv3 SQ pass of the same config and batch, tools/valu_pmc.py)
     valu = {}
@@ -594,44 +681,7 @@ def main():
         except Exception:
             traffic = None
 
-    # pose accuracy vs ground truth (sanity) and vs the CPU reference path (metric)
-    err_gt = np.abs(poses[:, 3:] - gts[:, 3:].astype(np.float32)).max()
-    result = {
-        "metric": METRIC,
-        "value": round(value, 3),
-        "unit": "scans/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "strong" if args.total_jobs else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": f"{cfg}: {H}x{W} {WORKLOAD[cfg]}; " + (
-                f"{args.total_jobs} independent scan-to-map jobs per step split over {world} GPU(s) (C4)"
-                if args.total_jobs else f"{B} independent scan-to-map jobs per GPU per step (C4-style independent jobs)"),
-            "jobs_per_step": int(sum(counts)),
-            "jobs_per_gpu_per_step": B,
-            "mean_points_per_scan": round(tot["n_in"] / B, 1),
-            "mean_local_map_points": round(tot["M"] / B, 1),
-            "mean_queries_per_scan": round(tot["Q"] / B, 1),
-            "mean_gn_iterations": round(float(stats["iterations"].mean()), 3),
-            "parallelism": (f"scan-shard x{world}, " + ("RCCL pose all-gather through the C-ABI (fbr_batch_allgather)"
-                                                         if native else f"{'RCCL' if args.backend == 'nccl' else 'gloo'} "
-                                                                        "pose all-gather (torch.distributed)")
-                            if dist is not None else "single GPU"),
-            "imu_deskew": bool(args.deskew),
-            "exact_voxel_order": int(args.exact_voxel_order),
-            "timed_region": ("fbr_batch_launch of a staged batch, every stage on the device: projection, features, "
-                             "per-ring and mapping VoxelGrids, CropBox statistics, Gauss-Newton registration, "
-                             "results; excludes the host-to-device copy of the raw scans and guesses "
-                             "(fbr_batch_stage: inputs resident in HBM as 16-B x, y, z, ring records packed "
-                             "by host threads, as the ingest path's records are), reported separately as "
-                             "the ingest line"),
-        },
+    result.update({
         "roofline": {
             "bound": "valu" if valu_bound else "hbm",
             "kernel": dom,
@@ -661,14 +711,7 @@ def main():
             "kernels": {k: {kk: v for kk, v in r.items() if kk != "live"} for k, r in kroof.items()},
         },
         "kernel_ms_per_step": {k: round(v[0], 4) for k, v in prof.items()},  # profiled untimed step
-        "path_bytes_per_step": tb,
-        "path_achieved_GBps": round(tb / (elapsed / args.steps) / 1e9, 2),
-        "path_frac_of_peak": round(tb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 5),
-        "max_abs_trans_err_vs_gt_m": float(err_gt),
-        "registration_status_ok": int((stats["status"] == 0).sum()),
-    }
-    if records_check is not None:
-        result["records_check"] = records_check
+    })
 
     if world == 1 and args.latency > 0:
         result["latency"] = latency_line(cfg, corner_map, surf_map, args.latency,

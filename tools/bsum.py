@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the headline of bench.py JSON lines found in the given log files."""
+"""Print the headline of `bench.py --full` JSON lines found in the given log files."""
 import json
 import sys
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """How much the path's kernels run side by side, from a rocprofv3 --kernel-trace CSV of the bench.
 
-Over the timed region of a `bench.py --steps STEPS` run (from the k_project dispatch of the first
+Over the timed region of a `bench.py --full --steps STEPS` run (from the k_project dispatch of the first
 timed launch -- the last STEPS of them -- to the end of the last kernel; pipelined launches make
 the gaps between k_project dispatches uneven, so only the whole region is divided by STEPS), per
 kernel family: summed dispatch time per launch, the part of it during which no other kernel ran

@@ -10,7 +10,7 @@ if [ -n "$SEL" ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "$SEL" > $OUT/pytest.txt 2>&1 || { tail -40 $OUT/pytest.txt; exit 10; }
   tail -1 $OUT/pytest.txt
 fi
-B="bench.py --steps 10 --warmup 2 --latency 20 --ingest 0 --exact-line 0 --no-cpu-baseline"
+B="bench.py --full --steps 10 --warmup 2 --latency 20 --ingest 0 --exact-line 0 --no-cpu-baseline"
 for r in $(seq 1 $REPS); do for v in a b; do
   E="FBR_AB=a"; [ $v = b ] && E="$ENVB"
   env $E timeout -k 10 300 python3 $B > $OUT/${v}_$r.json 2> $OUT/${v}_$r.err || { tail $OUT/${v}_$r.err; exit 13; }
@@ -20,7 +20,7 @@ print('$v $r', d['value'], d['ms_per_step'], 'lat', l.get('ms_per_scan_p50'), {a
 done; done
 for v in a b; do
   E="FBR_AB=a"; [ $v = b ] && E="$ENVB"
-  env $E timeout -k 10 300 python3 bench.py --config C3 --batch 256 --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/c3_$v.json 2>/dev/null || exit 18
+  env $E timeout -k 10 300 python3 bench.py --full --config C3 --batch 256 --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/c3_$v.json 2>/dev/null || exit 18
   python3 -c "
 import json; d=json.loads(open('$OUT/c3_$v.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('C3 $v', d['value'], {a: round(b,3) for a,b in k.items() if a in ('project','extract')})"

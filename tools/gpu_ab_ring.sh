@@ -12,8 +12,8 @@ lib() { if [ $1 = prev ]; then echo $PKG/libfbr_hip_prev.so; else echo $PKG/libf
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "voxel or ring or exact or order" > $OUT/pytest.txt 2>&1 || { tail -40 $OUT/pytest.txt; exit 10; }
 tail -1 $OUT/pytest.txt
 for rep in $(seq 1 $REPS); do for v in new prev; do
-  FBR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --latency 50 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/d_${v}_$rep.json 2>/dev/null || exit 17
-  FBR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --exact-voxel-order 1 > $OUT/x_${v}_$rep.json 2>/dev/null || exit 18
+  FBR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 2 --latency 50 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/d_${v}_$rep.json 2>/dev/null || exit 17
+  FBR_LIB=$(lib $v) timeout -k 10 300 python3 bench.py --full --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --exact-voxel-order 1 > $OUT/x_${v}_$rep.json 2>/dev/null || exit 18
   python3 -c "
 import json
 d=json.loads(open('$OUT/d_${v}_$rep.json').read().strip().splitlines()[-1]); x=json.loads(open('$OUT/x_${v}_$rep.json').read().strip().splitlines()[-1])

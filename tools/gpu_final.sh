@@ -8,7 +8,7 @@ timeout -k 10 1500 python -u -m pytest tests -m gpu -x -v --timeout 900 --timeou
 tail -2 $OUT/pytest_gpu.txt
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1 || { tail -20 $OUT/smoke.txt; exit 11; }
 tail -1 $OUT/smoke.txt
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 12; }
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 12; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 r=d['roofline']; print('BENCH', d['value'], d['ms_per_step'], r['bound'], r['kernel'], r['frac'], r.get('hbm_frac'))

@@ -6,7 +6,7 @@ set -o pipefail
 export TMPDIR=/tmp
 TAG=$1; REPS=$2; shift 2
 OUT=gpurun_out/$TAG; mkdir -p $OUT
-B="bench.py --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline ${BENCH_ARGS}"
+B="bench.py --full --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline ${BENCH_ARGS}"
 for r in $(seq 1 $REPS); do v=0; for E in "" "$@"; do
   N=v${v}_$r; v=$((v + 1))
   env $E timeout -k 10 300 python3 $B > $OUT/$N.json 2> $OUT/$N.err || { tail $OUT/$N.err; exit 13; }

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$1; KF=${2:-k_gn_knn}
 mkdir -p $OUT
 PKG=$PWD/feature_base_pointcloud_registration_amd
-CMD="bench.py --steps 4 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --profile off"
+CMD="bench.py --full --steps 4 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --profile off"
 for v in new prev; do
   if [ $v = prev ]; then export FBR_LIB=$PKG/libfbr_hip_prev.so; else export FBR_LIB=$PKG/libfbr_hip.so; fi
   timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE -d $OUT/sq_$v -o bench --output-format csv -- python3 $CMD > $OUT/sq_$v.log 2>&1 || { tail $OUT/sq_$v.log; exit 11; }

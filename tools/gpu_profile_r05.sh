@@ -16,7 +16,7 @@ if [ "$2" != "skip-tests" ]; then
   timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { cat $OUT/smoke.txt; exit 9; }
   cat $OUT/smoke.txt
 fi
-CMD="bench.py --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
+CMD="bench.py --full --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
 pmc() {  # name, counters...
   local name=$1; shift
   timeout -s KILL 300 rocprofv3 --pmc "$@" -d $OUT/$name -o bench --output-format csv -- python3 $CMD --profile off > $OUT/bench_$name.log 2>&1 || { tail $OUT/bench_$name.log; return 1; }
@@ -42,13 +42,13 @@ echo trace done
 python3 tools/roofline_check.py $(find $OUT/trace -name "*kernel_stats.csv" | head -1) $OUT/bench_trace.log --trace $(find $OUT/trace -name "*kernel_trace.csv" | head -1) > $OUT/roofline_check.txt 2>&1 || exit 23
 python3 tools/concurrency.py $(find $OUT/trace -name "*kernel_trace.csv" | head -1) 6 > $OUT/concurrency.txt 2>&1 || exit 24
 cat $OUT/roofline_check.txt $OUT/concurrency.txt
-C5="bench.py --config C5 --batch 16 --steps 3 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
+C5="bench.py --full --config C5 --batch 16 --steps 3 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
 timeout -s KILL 400 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $OUT/sq_c5 -o bench --output-format csv -- python3 $C5 --profile off > $OUT/bench_sq_c5.log 2>&1 || exit 25
 python3 tools/valu_pmc.py $(find $OUT/sq_c5 -name "*counter_collection.csv") C5 16 $OUT/valu_pmc_c5.json > $OUT/valu_pmc_c5.txt || exit 26
 cp $OUT/valu_pmc_c5.json profiles/valu_pmc_c5.json
 timeout -k 10 400 python3 $C5 --valu-json profiles/valu_pmc_c5.json > $OUT/bench_c5.json 2> $OUT/bench_c5.err || exit 27
-timeout -k 10 400 python3 bench.py --config C3 --batch 256 --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err || exit 28
-timeout -k 10 900 python3 bench.py > $OUT/bench_final.json 2> $OUT/bench_final.err || exit 29
+timeout -k 10 400 python3 bench.py --full --config C3 --batch 256 --steps 6 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/bench_c3.json 2> $OUT/bench_c3.err || exit 28
+timeout -k 10 900 python3 bench.py --full > $OUT/bench_final.json 2> $OUT/bench_final.err || exit 29
 python3 -c "
 import json; d=json.loads(open('$OUT/bench_final.json').read().strip().splitlines()[-1])
 r=d['roofline']; print('FINAL', d['value'], d['ms_per_step'], r['bound'], r['kernel'], r['frac'], r.get('hbm_frac'), r.get('valu_frac'), r.get('traffic'))

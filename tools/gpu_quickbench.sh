@@ -12,11 +12,11 @@ if [ "$SEL" != "none" ]; then
   timeout -k 10 600 python -u -m pytest $SEL -m gpu -x -q --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1 || { tail -30 $OUT/pytest.log; exit 21; }
   tail -2 $OUT/pytest.log
 fi
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit 22
-FBR_NSUB=1 timeout -k 10 300 python3 bench.py --batch 256 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/seq.json 2>> $OUT/bench.err || exit 23
+timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit 22
+FBR_NSUB=1 timeout -k 10 300 python3 bench.py --full --batch 256 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/seq.json 2>> $OUT/bench.err || exit 23
 if [ "${PMC:-0}" = "1" ]; then
-  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o b --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --profile off > $OUT/fetch.log 2>&1 || exit 24
-  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o b --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --profile off > $OUT/write.log 2>&1 || exit 25
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o b --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --profile off > $OUT/fetch.log 2>&1 || exit 24
+  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE -d $OUT/write -o b --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --profile off > $OUT/write.log 2>&1 || exit 25
   python3 tools/hbm_traffic.py $(find $OUT/fetch -name "*counter_collection.csv") $(find $OUT/write -name "*counter_collection.csv") C2 1024 $OUT/hbm_traffic.json || exit 26
 fi
 python3 - "$OUT" <<'EOF'

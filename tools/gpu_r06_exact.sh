@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/${1:-r06x}; mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread -k "voxel_order or exact or voxel_grid" > $OUT/pytest.txt 2>&1 || { tail -40 $OUT/pytest.txt; exit 10; }
 tail -1 $OUT/pytest.txt
-B="bench.py --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
+B="bench.py --full --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
 summ() { python3 -c "
 import json,sys; d=json.loads(open('$1').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('$2', d['value'], d['ms_per_step'], {a: round(b,3) for a,b in k.items() if b > 0.01})"; }

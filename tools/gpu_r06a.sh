@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/r06a; mkdir -p $OUT
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeout-method thread > $OUT/pytest.txt 2>&1 || { tail -40 $OUT/pytest.txt; exit 10; }
 tail -1 $OUT/pytest.txt
-B="bench.py --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
+B="bench.py --full --steps 10 --warmup 2 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline"
 summ() { python3 -c "
 import json,sys; d=json.loads(open('$1').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('$2', d['value'], d['ms_per_step'], {a: round(b,3) for a,b in k.items()})"; }
@@ -22,6 +22,6 @@ for r in 1 2; do
 done
 timeout -k 10 300 python3 $B --exact-voxel-order 1 > $OUT/exact.json 2> $OUT/exact.err || { tail $OUT/exact.err; exit 14; }
 summ $OUT/exact.json "exact B1024"
-timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --latency 100 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/lat.json 2> $OUT/lat.err || { tail $OUT/lat.err; exit 15; }
+timeout -k 10 300 python3 bench.py --full --steps 10 --warmup 2 --latency 100 --ingest 0 --exact-line 0 --no-cpu-baseline > $OUT/lat.json 2> $OUT/lat.err || { tail $OUT/lat.err; exit 15; }
 python3 -c "
 import json; d=json.loads(open('$OUT/lat.json').read().strip().splitlines()[-1]); print('latency', d['value'], d['latency'])"

@@ -9,7 +9,7 @@ tail -1 $OUT/pytest.txt
 timeout -k 10 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1 || { cat $OUT/smoke.txt; exit 9; }
 cat $OUT/smoke.txt
 for r in 1 2; do
-timeout -k 10 400 python3 bench.py --no-cpu-baseline --exact-line 0 --latency 100 > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { tail $OUT/bench_$r.err; exit 11; }
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --exact-line 0 --latency 100 > $OUT/bench_$r.json 2> $OUT/bench_$r.err || { tail $OUT/bench_$r.err; exit 11; }
 python3 -c "
 import json; d=json.loads(open('$OUT/bench_$r.json').read().strip().splitlines()[-1]); k=d['kernel_ms_per_step']
 print('bench', d['value'], d['ms_per_step'], {a: round(b,3) for a,b in k.items()})

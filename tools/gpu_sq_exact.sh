@@ -4,7 +4,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-r06sqx}; mkdir -p $OUT
-CMD="bench.py --batch 256 --steps 2 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --profile off --exact-voxel-order 1"
+CMD="bench.py --full --batch 256 --steps 2 --warmup 1 --latency 0 --ingest 0 --exact-line 0 --no-cpu-baseline --profile off --exact-voxel-order 1"
 pmc() { local name=$1; shift
   timeout -s KILL 300 rocprofv3 --pmc "$@" -d $OUT/$name -o bench --output-format csv -- python3 $CMD > $OUT/bench_$name.log 2>&1 || { tail $OUT/bench_$name.log; return 1; }; }
 pmc sqa SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_VMEM GRBM_GUI_ACTIVE || exit 15

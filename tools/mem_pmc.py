@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Vector-memory pipeline of the path kernels from one rocprofv3 pass:
 `rocprofv3 --pmc TA_TA_BUSY TA_FLAT_READ_WAVEFRONTS TCP_TOTAL_CACHE_ACCESSES TCP_TCC_READ_REQ
-TCP_TCP_LATENCY TCP_TCC_READ_REQ_LATENCY GRBM_GUI_ACTIVE -- python3 bench.py ...`
+TCP_TCP_LATENCY TCP_TCC_READ_REQ_LATENCY GRBM_GUI_ACTIVE -- python3 bench.py --full ...`
 (2 TA + 4 TCP + 1 GRBM counters; rocprofv3 serialises the pass's dispatches).
 
 Per launcher (bench.py's kernel families), per launch:

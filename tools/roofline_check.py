@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Recompute bench.py's roofline fractions from a rocprofv3 --stats kernel summary.
+"""Recompute the roofline fractions of a `bench.py --full` line from a rocprofv3 --stats kernel summary.
 
 bench.py times every kernel family with the dispatches' own start / end timestamps; rocprofv3's
 kernel trace reports the same per-dispatch durations.  This script takes a committed
@@ -10,7 +10,7 @@ carries them, the VALU-issue fraction each gives for the bench's VALU instructio
 (rocprofv3 SQ pass, tools/valu_pmc.py) against the measured issue peak (profiles/valu_calib.json).
 
 With --trace KERNEL_TRACE.csv (the same run's rocprofv3 kernel trace) the rocprofv3 column covers
-the timed region only: per launcher, the dispatches after the untimed launches' share (bench.py runs
+the timed region only: per launcher, the dispatches after the untimed launches' share (bench.py --full runs
 `warmup` launches, then one profiled launch alone, then the `steps` timed ones; k_project dispatches
 count the launches).  The stats summary averages the untimed launches too, which run with fewer
 launches beside them, so their kernels are shorter than the overlapped ones the bench times.

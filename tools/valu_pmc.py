@@ -2,7 +2,7 @@
 """Per-launch VALU work of the path kernels from a rocprofv3 SQ counter pass -> profiles/valu_pmc.json.
 
 Input: the counter_collection.csv of `rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES
-SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py ...` (one pass: 4 SQ + 1 GRBM counters; rocprofv3
+SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -- python3 bench.py --full ...` (one pass: 4 SQ + 1 GRBM counters; rocprofv3
 serialises a counter pass's dispatches, so every kernel runs alone).  Per launcher (bench.py's
 kernel families; a launcher of two kernels counts its calls once):
 
