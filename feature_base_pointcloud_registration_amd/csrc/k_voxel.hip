@@ -305,11 +305,18 @@ __device__ __attribute__((always_inline)) void vg_radix_sort_inplace(FBR_LDS_AS 
   const int nbins = 1 << dbits, tot = nbins * NW;
   const int chunk = (((n + NW - 1) / NW) + 63) & ~63;
   const int c0 = min(n, w * chunk), c1 = min(n, c0 + chunk);
+  // The product form (kLeader 0) leaves the load, count and scatter loops at the wave's first
+  // empty step (a C2 surf cloud fills 14 of its waves' 18 steps, a corner cloud 5 of 16, a part of
+  // the split kernel fewer), and an empty step still costs its ballots.  (Round 5 replayed this
+  // exit three ways without a mis-sort)
+  constexpr bool kSkip = kLeader == 0;
   uint32_t kr[KPL], vr[KPL];
   for (int pass = 0; pass < passes; ++pass) {
     const int shift = dbits * pass;
 #pragma unroll
     for (int k = 0; k < KPL; ++k) {
+      if constexpr (kSkip)
+        if (c0 + 64 * k >= c1) break;  // wave-uniform
       const int i = c0 + 64 * k + lane;
       kr[k] = i < c1 ? keys[i] : 0u;
       vr[k] = i < c1 ? vals[i] : 0u;
@@ -333,8 +340,11 @@ __device__ __attribute__((always_inline)) void vg_radix_sort_inplace(FBR_LDS_AS 
       }
     } else {
 #pragma unroll
-      for (int k = 0; k < KPL; ++k)
+      for (int k = 0; k < KPL; ++k) {
+        if constexpr (kSkip)
+          if (c0 + 64 * k >= c1) break;  // wave-uniform
         if (c0 + 64 * k + lane < c1) atomicAdd(&hist[w * NB + ((kr[k] >> shift) & dmask)], 1u);
+      }
     }
     __syncthreads();
     {
@@ -365,7 +375,7 @@ __device__ __attribute__((always_inline)) void vg_radix_sort_inplace(FBR_LDS_AS 
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < KPL; ++k) {
-      if constexpr (kLeader == 2)
+      if constexpr (kLeader == 2 || kSkip)
         if (c0 + 64 * k >= c1) break;  // wave-uniform: the rest of the chunk is empty
       const bool valid = c0 + 64 * k + lane < c1;
       const uint32_t d = (kr[k] >> shift) & dmask;
@@ -1552,6 +1562,23 @@ size_t voxel_lds_bytes(const VgArgs& a, int threads, bool lds_mode) {
 }
 
 constexpr int kVgIpKpl = 18;  // k_voxel_grid_ip: segments up to 1024 * 18 points sort in LDS
+// Size classes of a two-set launch (batch mapping DS).  The 1024 x 18 instance needs 146 KB of LDS,
+// so a CU holds one workgroup of it and nothing else that uses LDS.  A set of small capacity (the
+// corner clouds: at most kCornerPerRing picks per ring, and about a third of that in practice) gets
+// its own launch of a 256-thread instance that sorts 256 * 16 = 4,096 points in 35 KB: four
+// workgroups per CU.  Larger clouds of such a set take that instance's global-scratch branch.
+// FBR_VG_CLASSES: 0 = one launch of the large instance for both sets, 1 = the small set's launch
+// first (default), 2 = last.
+constexpr int kVgIpSmallT = 256, kVgIpSmallKpl = 16;
+constexpr int64_t kVgIpSmallSetCap = 4 * kVgIpSmallT * kVgIpSmallKpl;
+int vg_classes() {
+  static const int v = [] {
+    const char* e = std::getenv("FBR_VG_CLASSES");
+    const int c = e ? std::atoi(e) : 1;
+    return c < 0 || c > 2 ? 1 : c;
+  }();
+  return v;
+}
 constexpr int kVgSplitSlots = 16;   // k_voxel_grid_split: segments x parts per launch
 constexpr int kVgSplitRing = 1024;  // flag regions: a launch's own region (concurrent launches)
 constexpr int kVgSplitMaxDevices = 64;
@@ -1606,9 +1633,30 @@ void launch_voxel_grid(hipStream_t s, const VgArgs& a) {
     if (cap <= kVgLdsCap) {
       fbr_launch((k_voxel_grid<256, uint16_t, true, E>), dim3(nseg), dim3(256), voxel_lds_bytes(a, 256, true), s, a);
     } else if (vg_inplace()) {
-      const size_t lds =
-          voxel_lds_bytes(a, 1024, false) + (size_t)1024 * kVgIpKpl * (sizeof(uint32_t) + sizeof(uint16_t));
-      fbr_launch((k_voxel_grid_ip<1024, kVgIpKpl, E>), dim3(nseg), dim3(1024), lds, s, a);
+      constexpr size_t pair = sizeof(uint32_t) + sizeof(uint16_t);
+      const size_t lds = voxel_lds_bytes(a, 1024, false) + (size_t)1024 * kVgIpKpl * pair;
+      // Two sets (the mapping DS of a batch: surf and corner clouds), one of them of the small
+      // class: one launch per set, the instance by the set's own capacity.  Sets of one class
+      // share a launch (two launches of one instance only serialise them on the stream).
+      const int cls = vg_classes();
+      int small = -1;
+      for (int k = 0; k < 2 && cls != 0; ++k)
+        if (a.s[0].nseg > 0 && a.s[1].nseg > 0 && a.s[k].cap <= kVgIpSmallSetCap && a.s[k].cap < a.s[1 - k].cap) small = k;
+      if (small < 0) {
+        fbr_launch((k_voxel_grid_ip<1024, kVgIpKpl, E>), dim3(nseg), dim3(1024), lds, s, a);
+        return;
+      }
+      const int first = cls == 1 ? small : 1 - small;
+      for (int k : {first, 1 - first}) {
+        VgArgs one{};
+        one.s[0] = a.s[k];
+        one.err = a.err;
+        if (k == small)
+          fbr_launch((k_voxel_grid_ip<kVgIpSmallT, kVgIpSmallKpl, E>), dim3(one.s[0].nseg), dim3(kVgIpSmallT),
+                     voxel_lds_bytes(one, kVgIpSmallT, false) + (size_t)kVgIpSmallT * kVgIpSmallKpl * pair, s, one);
+        else
+          fbr_launch((k_voxel_grid_ip<1024, kVgIpKpl, E>), dim3(one.s[0].nseg), dim3(1024), lds, s, one);
+      }
     } else {
       fbr_launch((k_voxel_grid<1024, uint32_t, false, E>), dim3(nseg), dim3(1024), voxel_lds_bytes(a, 1024, false),
                  s, a);
@@ -1707,7 +1755,8 @@ void launch_concat(hipStream_t s, int B, int H, int W, const float4* corner_slot
 // variant 0: vg_radix_sort<512, u16, 8, LDS> (per-ring filter), 1: vg_radix_sort<256, u16, 9, LDS>
 // (per-segment LDS kernel), 2: vg_radix_sort<1024, u32, 9, global> (global-scratch kernel),
 // 3: vg_radix_sort_inplace<1024, 18> (mapping DS), 4: the same with ballot-leader digit counts,
-// 5: round 3's rejected form (ballot-leader counts + wave-uniform early exits).
+// 5: round 3's rejected form (ballot-leader counts + wave-uniform early exits),
+// 6: vg_radix_sort_inplace<256, 16> (the small size class of the mapping DS).
 template <int T, typename V, int MAXD, bool KV_LDS>
 __global__ void __launch_bounds__(T) k_selftest_radix(uint32_t* keys, uint32_t* vals, uint32_t* scratch, int n, int nbits) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1741,23 +1790,23 @@ __global__ void __launch_bounds__(T) k_selftest_radix(uint32_t* keys, uint32_t* 
   }
 }
 
-template <int kLeader>
-__global__ void __launch_bounds__(1024) k_selftest_radix_ip(uint32_t* keys, uint32_t* vals, int n, int nbits) {
+template <int kLeader, int T = 1024, int KPL = kVgIpKpl>
+__global__ void __launch_bounds__(T) k_selftest_radix_ip(uint32_t* keys, uint32_t* vals, int n, int nbits) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int NW = 16, LCAP = 1024 * kVgIpKpl;
+  constexpr int NW = T / 64, LCAP = T * KPL;
   uint32_t* hist = (uint32_t*)smem;
   uint32_t* wsum = hist + (NW + 1) * 512;
   unsigned char* q = (unsigned char*)(wsum + NW);
   q = smem + (((q - smem) + 15) & ~15);
   FBR_LDS_AS uint32_t* k = (FBR_LDS_AS uint32_t*)q;
   FBR_LDS_AS uint16_t* v = (FBR_LDS_AS uint16_t*)((FBR_LDS_AS uint32_t*)q + LCAP);
-  for (int i = threadIdx.x; i < n; i += 1024) {
+  for (int i = threadIdx.x; i < n; i += T) {
     k[i] = keys[i];
     v[i] = (uint16_t)i;
   }
   __syncthreads();
-  vg_radix_sort_inplace<1024, kVgIpKpl, kLeader>(k, v, n, nbits, hist, wsum);
-  for (int i = threadIdx.x; i < n; i += 1024) {
+  vg_radix_sort_inplace<T, KPL, kLeader>(k, v, n, nbits, hist, wsum);
+  for (int i = threadIdx.x; i < n; i += T) {
     keys[i] = k[i];
     vals[i] = v[i];
   }
@@ -1770,8 +1819,9 @@ __global__ void __launch_bounds__(1024) k_selftest_radix_ip(uint32_t* keys, uint
 // each sorted position.
 extern "C" int fbr_selftest_radix_sort(int64_t n, int nbits, int variant, uint32_t* keys_inout, uint32_t* perm) {
   using namespace fbr;
-  const int64_t lcap[6] = {4096, 4096, 1 << 20, 1024 * kVgIpKpl, 1024 * kVgIpKpl, 1024 * kVgIpKpl};
-  if (n < 0 || variant < 0 || variant > 5 || n > lcap[variant] || nbits < 1 || nbits > 32 || (n && (!keys_inout || !perm)))
+  const int64_t lcap[7] = {4096, 4096, 1 << 20, 1024 * kVgIpKpl, 1024 * kVgIpKpl, 1024 * kVgIpKpl,
+                           kVgIpSmallT * kVgIpSmallKpl};
+  if (n < 0 || variant < 0 || variant > 6 || n > lcap[variant] || nbits < 1 || nbits > 32 || (n && (!keys_inout || !perm)))
     return FBR_ERR_INVALID_ARG;
   if (n == 0) return FBR_OK;
   uint32_t *dk = nullptr, *dv = nullptr, *ds = nullptr;
@@ -1794,6 +1844,10 @@ extern "C" int fbr_selftest_radix_sort(int64_t n, int nbits, int variant, uint32
       case 2:
         hipLaunchKernelGGL((k_selftest_radix<1024, uint32_t, 9, false>), dim3(1), dim3(1024), hdr(1024), 0, dk, dv, ds,
                            nn, nbits);
+        break;
+      case 6:
+        hipLaunchKernelGGL((k_selftest_radix_ip<0, kVgIpSmallT, kVgIpSmallKpl>), dim3(1), dim3(kVgIpSmallT),
+                           hdr(kVgIpSmallT) + (size_t)kVgIpSmallT * kVgIpSmallKpl * 6, 0, dk, dv, nn, nbits);
         break;
       default: {
         const size_t lds = hdr(1024) + (size_t)1024 * kVgIpKpl * 6;

@@ -498,7 +498,8 @@ int fbr_selftest_voxel_order(int64_t n, const uint32_t* keys, int lds, uint32_t*
  * 8-bit digits, n <= 4096), 1 = the per-segment LDS sort (256 threads, 9-bit digits, n <= 4096),
  * 2 = the global-scratch sort (1024 threads), 3 = the mapping DS's in-place LDS sort (1024 x 18),
  * 4 = variant 3 with ballot-leader digit counts, 5 = variant 4 with round 3's wave-uniform early
- * exits in its count and scatter loops (the exact form round 3 reverted).  keys_inout receives
+ * exits in its count and scatter loops (the exact form round 3 reverted), 6 = the in-place sort
+ * of the mapping DS's small size class (256 x 16, n <= 4096).  keys_inout receives
  * the sorted keys, perm the source index of every sorted position. */
 int fbr_selftest_radix_sort(int64_t n, int nbits, int variant, uint32_t* keys_inout, uint32_t* perm);
 
