@@ -578,6 +578,19 @@ class Context:
         _check(lib().fbr_batch_labels(self._h, int(job), ptr(out), len(out), ctypes.byref(n)), "fbr_batch_labels")
         return out[:n.value]
 
+    def feature_paths(self):
+        """Tests: which walk each ring segment of the k_features launches since the last call took
+        (fbr_diag_feature_paths; FeatArgs::paths in csrc/fbr_kernels.h gives the encoding): uint32
+        [launch slots * max_batch, n_scan], zero where no ring ran.  The first call only arms the
+        record."""
+        f = lib().fbr_diag_feature_paths
+        f.restype, f.argtypes = ctypes.c_int, [_VP, _VP, _I64, _VP]
+        n = _I64()
+        _check(f(self._h, None, 0, ctypes.byref(n)), "fbr_diag_feature_paths")
+        out = np.zeros(max(n.value, 1), np.uint32)
+        _check(f(self._h, ptr(out), len(out), ctypes.byref(n)), "fbr_diag_feature_paths")
+        return out[:n.value].reshape(-1, self.params.n_scan)
+
     def batch_export(self, device_ptr):
         """Enqueue the 32 B/job pose records into device memory at `device_ptr` (int address)."""
         _check(lib().fbr_batch_export(self._h, ctypes.c_void_p(device_ptr)), "fbr_batch_export")

@@ -286,6 +286,7 @@ struct fbr_ctx {
   // ~870 workgroups (x 8 in the wide kNN mode) that found no item.
   int items_hint = 0;
   unsigned long long* d_feat_stamps = nullptr;  // diagnostic builds (FBR_FEAT_STAMPS) only
+  uint32_t* d_feat_paths = nullptr;             // tests (fbr_diag_feature_paths): FeatArgs::paths [Bwork][H]
   // IMU deskew (fbr_set_deskew)
   fbr_deskew_table* d_desk = nullptr;  // [Bcap] tables (allocated on first use)
   int32_t* d_desk_mode = nullptr;      // [Bcap] kDesk* bits per job
@@ -601,6 +602,28 @@ bool feat_surf_window() {
   return v;
 }
 
+// The greedy walks over compact bit words (FeatArgs::compact; FBR_FEAT_COMPACT=0: the
+// member-indexed rounds everywhere, for A/B).
+bool feat_compact() {
+  static const bool v = [] {
+    const char* e = std::getenv("FBR_FEAT_COMPACT");
+    return e ? std::atoi(e) != 0 : true;
+  }();
+  return v;
+}
+
+// Members the compact batch surf window resolves left of a segment's end: 59 (one word with the
+// frozen candidates; the measured best) or 64 (two words); FBR_FEAT_SURF_WIN overrides, for A/B.
+constexpr int kFeatSurfWinDefault = 59;
+int feat_surf_win() {
+  static const int v = [] {
+    const char* e = std::getenv("FBR_FEAT_SURF_WIN");
+    const int w = e ? std::atoi(e) : kFeatSurfWinDefault;
+    return w == 59 ? 59 : 64;
+  }();
+  return v;
+}
+
 // err_clear: stage_project has just cleared the jobs' feature-capacity flags (k_project).
 // labels_out: cloudLabel is an output of the call (fbr_extract_features), so every surf walk runs
 // whole; otherwise only the picks that reach something observable are resolved (FeatArgs).
@@ -635,6 +658,9 @@ int stage_features(fbr_ctx* c, const Sub& sb, bool stream_mode, bool err_clear =
   feat_caps(c->W, a);
   a.gscratch = c->d_feat_scratch + j0 * H * a.gslot_bytes;
   a.stamps = c->d_feat_stamps ? c->d_feat_stamps + j0 * H * 12 : nullptr;
+  a.compact = feat_compact() ? 1 : 0;
+  a.surf_win = feat_surf_win();
+  a.paths = c->d_feat_paths ? c->d_feat_paths + j0 * H : nullptr;
   if (!err_clear) CK(hipMemsetAsync(c->d_err + j0, 0, sizeof(int32_t) * sb.B, sb.st));
   TIMED_ON(c, sb.st, "features", launch_features(sb.st, a));
   if (!stream_mode && c->diag_err_job >= sb.in0 && c->diag_err_job < sb.in0 + sb.B)
@@ -1721,6 +1747,7 @@ int fbr_destroy(fbr_ctx* c) {
                   c->d_kf_c, c->d_kf_s, c->d_kraw_c, c->d_kraw_s, c->d_kds_c, c->d_kds_s, c->d_kf_segs, c->d_bounds, c->d_direct_done, c->d_pk};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  if (c->d_feat_paths) (void)hipFree(c->d_feat_paths);
   if (c->h_iter_flags) (void)hipHostFree(c->h_iter_flags);
   free_grid(c->grid_c);
   free_grid(c->grid_s);
@@ -2843,6 +2870,27 @@ extern "C" int fbr_diag_feature_stamps(fbr_ctx* c, unsigned long long* out /* [m
     return FBR_OK;
   }
   if (out) CK(fbr_memcpy_sync(out, c->d_feat_stamps, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost));
+  return FBR_OK;
+}
+
+// Tests: which walk every segment of the k_features launches since the last call took
+// (FeatArgs::paths).  The first call allocates the record; later calls copy it out ([every
+// launch slot's jobs][n_scan] words, cap >= that many) and clear it.
+extern "C" int fbr_diag_feature_paths(fbr_ctx* c, uint32_t* out, int64_t cap, int64_t* n_out) {
+  if (!c) return FBR_ERR_INVALID_ARG;
+  CK(enter(c));
+  const size_t n = (size_t)c->Bwork * c->H;
+  if (n_out) *n_out = (int64_t)n;
+  if (!c->d_feat_paths) {
+    CK(hipMalloc(&c->d_feat_paths, sizeof(uint32_t) * n));
+    CK(hipMemset(c->d_feat_paths, 0, sizeof(uint32_t) * n));
+    return FBR_OK;
+  }
+  if (!out) return FBR_OK;
+  if (cap < (int64_t)n) return FBR_ERR_CAPACITY;
+  CK(hipDeviceSynchronize());
+  CK(fbr_memcpy_sync(out, c->d_feat_paths, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  CK(hipMemset(c->d_feat_paths, 0, sizeof(uint32_t) * n));
   return FBR_OK;
 }
 

@@ -140,6 +140,17 @@ struct FeatArgs {
   // Batch jobs start from a fresh node: labels at indices < 5 are written even when 0 (no stale
   // value to keep), so the label buffer needs no clearing between launches.
   int fresh = 0;
+  // 1: the greedy walks run over compact bit words (k_features.hip, "compact walks"): the corner
+  // walk over the list of a segment's corner candidates (<= 128, else the member-indexed rounds),
+  // the batch surf window over the bits re-based at its first frozen member.  0
+  // (FBR_FEAT_COMPACT=0): the member-indexed rounds everywhere, window 64.
+  int compact = 1;
+  int surf_win = 59;     // compact batch surf window, members resolved left of ep: 59 (one word) or 64
+  // tests only (fbr_diag_feature_paths), null in normal launches: [B][H] one word per ring, which
+  // walk each segment j took: bits 4j..4j+1 corner (0 one word, 1 two words, 2 member-indexed,
+  // 3 stale-slot walk), bits 4j+2..4j+3 surf (0 skipped, 1 window, 2 whole walk after the window
+  // left a member near ep undecided, 3 whole walk), bit 24+j: segment j is not empty.
+  uint32_t* paths = nullptr;
 };
 size_t features_lds_bytes(const FeatArgs& a, int nwv);  // nwv: waves per ring
 size_t features_gslot_bytes(const FeatArgs& a);

@@ -27,7 +27,9 @@
 //     once every higher-priority conflicting candidate is "not taken", and "not taken" once one of
 //     them is taken — final decisions, identical to the sequential walk.  The corner cap keeps the
 //     first 20 taken in visit order.  The segment holding the stale slot keeps the sequential walk
-//     (its stale index may duplicate a member).
+//     (its stale index may duplicate a member).  Only candidates take part, so the rounds run over
+//     a dense numbering of them ("compact walks" below): the corner walk over the list of its
+//     candidates, the batch surf walk over the window re-based at its first frozen member.
 // Outputs: label (the feature mask) and per-ring corner slots in visit order; the per-ring surf
 // candidates (label <= 0, index order) are read from the mask by the per-ring VoxelGrid.
 #include "fbr_common.h"
@@ -223,6 +225,83 @@ __device__ __forceinline__ void greedy_rounds(int m, int lane, uint64_t (&und)[W
     }
     if (!any || (frz && !progress)) break;
     if (round > 4 * (m + 2)) {  // unreachable: each round decides the best-ranked undecided
+      if (lane == 0) atomicOr(&a.err[job], 8);
+      break;
+    }
+  }
+}
+
+// ---- compact walks ----
+// Only candidates ever enter und / tak, so the greedy independent set depends only on the
+// conflicts among candidates: the rounds can run over any dense numbering of them.  A numbering
+// that keeps member order keeps every conflict within +-5 positions, so a candidate's
+// higher-priority conflicts are 11 bits placed at its position in a one- or two-word set, and a
+// round is two ANDs against the wave-uniform tak / und words per candidate.
+struct U128 {
+  uint64_t lo, hi;
+};
+
+// rel (11 bits: bit 5 + k <-> position pos + k) placed in the 128-bit position set.
+__device__ __forceinline__ U128 place11(uint32_t rel, int pos) {
+  const int s = pos - 5;
+  U128 r;
+  if (s < 0) {
+    r.lo = (uint64_t)(rel >> (-s));
+    r.hi = 0ull;
+  } else if (s < 64) {
+    r.lo = (uint64_t)rel << s;
+    r.hi = s > 53 ? (uint64_t)rel >> (64 - s) : 0ull;
+  } else {
+    r.lo = 0ull;
+    r.hi = (uint64_t)rel << (s - 64);
+  }
+  return r;
+}
+
+__device__ __forceinline__ uint64_t readlane64(uint64_t v, int l);
+
+// Bits of the segment members [64k, 64k + 64) (members above m cleared) from a per-lane copy of
+// window bit words: lane l holds the word of window index li0 + 64 * l, sh = li0 & 63, li0 the
+// window index of member 0.  Wave-uniform: a segment's flags without a ballot per 64 members.
+__device__ __forceinline__ uint64_t member_bits(uint64_t wv, int sh, int k, int m) {
+  const uint64_t lo = readlane64(wv, k), hi = readlane64(wv, k + 1);
+  const uint64_t x = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+  const int rem = m - 64 * k;  // the chunk's last member
+  return rem >= 63 ? x : (rem < 0 ? 0ull : x & ((2ull << rem) - 1ull));
+}
+
+// greedy_rounds' rule over NH position words: lane l owns positions l (cf[0]) and 64 + l (cf[1]).
+// frz0: frozen positions of word 0 (they stay in und0 and block the positions they outrank); the
+// rounds stop when nothing live is left or a round decides nothing.
+template <int NH>
+__device__ __forceinline__ void compact_rounds(int lane, uint64_t& und0, uint64_t& und1, uint64_t& tak0, uint64_t& tak1,
+                                               const U128 (&cf)[NH], uint64_t frz0, int cap, const FeatArgs& a, int job) {
+  for (int round = 0;; ++round) {
+    bool progress = false;
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+      const uint64_t live = h == 0 ? und0 & ~frz0 : und1;
+      if (live != 0ull) {
+        const bool mine = (live >> lane) & 1ull;
+        const uint64_t clo = cf[h].lo, chi = NH > 1 ? cf[h].hi : 0ull;
+        bool nt = false, tk = false;
+        if (mine) {
+          if (((tak0 & clo) | (tak1 & chi)) != 0ull) nt = true;
+          else if (((und0 & clo) | (und1 & chi)) == 0ull) tk = true;
+        }
+        const uint64_t bt = __ballot(tk);
+        if (h == 0) tak0 |= bt;
+        else tak1 |= bt;
+        // suppressed by a position taken just now: decided in the same round (as greedy_rounds)
+        if (bt != 0ull && mine && !tk && !nt) nt = ((tak0 & clo) | (tak1 & chi)) != 0ull;
+        const uint64_t bn = __ballot(nt);
+        if (h == 0) und0 &= ~(bt | bn);
+        else und1 &= ~(bt | bn);
+        progress |= (bt | bn) != 0ull;
+      }
+    }
+    if (((und0 & ~frz0) | und1) == 0ull || !progress) break;
+    if (round > cap) {  // unreachable: each round decides the best-ranked live position or none
       if (lane == 0) atomicOr(&a.err[job], 8);
       break;
     }
@@ -692,6 +771,7 @@ k_features(FeatArgs a) {
     }
   };
   int lastj = -1;  // the ring's last non-empty segment
+  uint32_t rec = 0u;  // FeatArgs::paths
   for (int j = 0; j < 6; j++)
     if ((s * (6 - j) + e * j) / 6 < (s * (5 - j) + e * (j + 1)) / 6 - 1) lastj = j;
   for (int j = 0; j < 6; j++) {
@@ -719,7 +799,18 @@ k_features(FeatArgs a) {
     // without ties among those no sort is needed: priorities come from curvature comparisons
     // (corner walk: ep first, then descending; surf walk: the reverse).  The stale-slot segment
     // and segments with a relevant tie (their order is introsort's) take the sorted path.
+    // Corner candidates (!picked && edgec) of the members, as wave-uniform words, and their list cl
+    // in member order (region B behind the sorted path's order and ranks): built with the cm
+    // member list of batch segments, or by the corner walk; the sorted path overwrites it.
+    uint16_t* cl = (uint16_t*)(S.rb + 4 * segcap);
+    int nc_pre = -1;  // candidates listed in cl, -1: not listed
+    const int li0 = sp - S.wlo;
+    auto cand_words = [&]() __attribute__((always_inline)) {
+      const int w = (li0 >> 6) + lane;
+      return (lane <= WMAX && w < S.nw) ? ~S.picked.w[w] & S.edgec.w[w] : 0ull;
+    };
     auto sorted_order = [&]() __attribute__((always_inline)) {
+      nc_pre = -1;
       // -- sort [sp, ep) by (curvature bits, position) --
       int kpow = 1;
       while (kpow < m) kpow <<= 1;
@@ -844,6 +935,7 @@ k_features(FeatArgs a) {
     };
     const bool seg_full = a.surf_full || (a.carry && sp <= 9);  // the whole surf walk is observable
     const bool cm_sparse = !seg_full && !has_stale;
+    const int swin = a.compact ? a.surf_win : kSurfWindow;  // batch surf window
     bool direct = !has_stale;
 #ifdef FBR_FEAT_SKIP_CM
     if (direct) {
@@ -855,7 +947,7 @@ k_features(FeatArgs a) {
     if (direct) {
 #endif
       bool tf = false;
-      // Batch jobs need cm only for the corner candidates and the surf window [m - 63, m] (none
+      // Batch jobs need cm only for the corner candidates and the surf window [m - swin + 1, m] (none
       // for the surf walk of the ring's last segment): the members are listed in region B (free
       // until the corner walk) and only those are computed; the rest follow in the rare case the
       // surf window falls back to the whole walk (cm_rest below).
@@ -863,19 +955,23 @@ k_features(FeatArgs a) {
       if (cm_sparse) {
         uint16_t* list = (uint16_t*)S.rb;
         if (wv == 0) {
-          int cnt = 0;
-          const int wlo_u = j == lastj ? m + 1 : max(0, m - (kSurfWindow - 1));
-          for (int k0 = 0; k0 <= m; k0 += 64) {
-            const int u = k0 + lane;
-            bool need = false;
-            if (u <= m) {
-              const int li = sp + u - S.wlo;
-              need = u >= wlo_u || (!S.picked.get(li) && S.edgec.get(li));
-            }
-            const uint64_t bm = __ballot(need);
-            if (need) list[cnt + __popcll(bm & ((1ull << lane) - 1ull))] = (uint16_t)u;
-            cnt += __popcll(bm);
+          int cnt = 0, ncand = 0;
+          const int wlo_u = j == lastj ? m + 1 : max(0, m - (swin - 1));
+          const uint64_t cwv = cand_words();
+          const uint64_t ltm0 = (1ull << lane) - 1ull;
+          for (int k = 0; 64 * k <= m; ++k) {
+            const uint64_t cb = member_bits(cwv, li0 & 63, k, m);
+            const int lo = wlo_u - 64 * k;  // the surf window's members of this chunk
+            const int rem = m - 64 * k;
+            uint64_t wb = lo <= 0 ? ~0ull : (lo >= 64 ? 0ull : ~0ull << lo);
+            if (rem < 63) wb &= (2ull << rem) - 1ull;
+            const uint64_t nb = cb | wb;
+            if ((nb >> lane) & 1ull) list[cnt + __popcll(nb & ltm0)] = (uint16_t)(64 * k + lane);
+            if ((cb >> lane) & 1ull) cl[ncand + __popcll(cb & ltm0)] = (uint16_t)(64 * k + lane);
+            cnt += __popcll(nb);
+            ncand += __popcll(cb);
           }
+          nc_pre = ncand;
           if (lane == 0) S.tmask[15] = (uint64_t)cnt;
         }
         if constexpr (NWV == 1) wsync();
@@ -901,6 +997,7 @@ k_features(FeatArgs a) {
       FBR_STAMP(10);
     }
     if (wv == 0) {  // the walks: wave 0 alone (helper waves wait at the segment's closing barrier)
+    rec |= 1u << (24 + j);
     if (!direct) sorted_order();
     FBR_STAMP(3);
     if (has_stale) {
@@ -915,10 +1012,98 @@ k_features(FeatArgs a) {
         corner_cnt = __shfl(corner_cnt, 0);
         wsync();
       }
+      rec |= 15u << (4 * j);
     } else {
       // -- corner walk --
-      uint64_t und[WMAX], tak[WMAX];
-      auto corner_walk = [&]() __attribute__((always_inline)) {
+      // Both forms leave the taken corners (member order) in tlu / tlv on the direct path, and
+      // their member mask in S.tmask on the sorted one (whose cap scan walks the sorted order).
+      int T = 0;      // taken corners
+      int ccode = 0;  // path record
+      const uint64_t ltm = (1ull << lane) - 1ull;
+      // Compact form: the candidates are listed in member order (cl, region B behind the sorted
+      // path's order and ranks; tlu takes its place afterwards), list position q on lane q & 63.
+      // The 10-bit mask of a candidate's higher-priority conflicting members becomes 11 bits over
+      // list positions: a conflicting candidate d <= 5 members away is one of the <= 5 next list
+      // entries.  More than 128 candidates: the member-indexed rounds.
+      auto corner_compact = [&]() __attribute__((always_inline)) -> bool {
+        int nc = nc_pre;
+        if (nc < 0) {
+          nc = 0;
+          const uint64_t cwv = cand_words();
+          for (int k = 0; 64 * k <= m; ++k) {
+            const uint64_t cb = member_bits(cwv, li0 & 63, k, m);
+            if ((cb >> lane) & 1ull) cl[nc + __popcll(cb & ltm)] = (uint16_t)(64 * k + lane);
+            nc += __popcll(cb);
+          }
+        }
+        if (nc > 128) return false;
+        T = 0;
+        ccode = nc > 64 ? 1 : 0;
+        if (nc == 0 && direct) return true;
+        wsync();
+        auto run = [&](auto NHc) __attribute__((always_inline)) {
+          constexpr int NH = decltype(NHc)::value;
+          U128 cf[NH];
+          int uu[NH];
+#pragma unroll
+          for (int h = 0; h < NH; ++h) {
+            const int q = 64 * h + lane;
+            uint32_t rel = 0u;
+            int u = 0;
+            if (q < nc) {
+              u = cl[q];
+              const uint32_t c10 = S.cm[u] & 1023u;
+              int un[10];
+#pragma unroll
+              for (int k = 1; k <= 5; ++k) {  // independent LDS reads, then the masks
+                un[4 + k] = cl[min(q + k, nc - 1)];
+                un[5 - k] = cl[max(q - k, 0)];
+              }
+#pragma unroll
+              for (int k = 1; k <= 5; ++k) {
+                const int df = min(un[4 + k] - u, 6), db = min(u - un[5 - k], 6);
+                if (q + k < nc && df <= 5 && ((c10 >> (4 + df)) & 1u)) rel |= 1u << (5 + k);
+                if (q - k >= 0 && db <= 5 && ((c10 >> (5 - min(db, 5))) & 1u)) rel |= 1u << (5 - k);
+              }
+            }
+            uu[h] = u;
+            cf[h] = place11(rel, q);
+          }
+          uint64_t und0 = nc >= 64 ? ~0ull : (1ull << nc) - 1ull;
+          uint64_t und1 = NH > 1 ? (nc >= 128 ? ~0ull : (1ull << (nc - 64)) - 1ull) : 0ull;
+          uint64_t tak0 = 0ull, tak1 = 0ull;
+#ifndef FBR_FEAT_SKIP_CORNER
+          compact_rounds<NH>(lane, und0, und1, tak0, tak1, cf, 0ull, 4 * (nc + 2), a, job);
+#endif
+          T = __popcll(tak0) + __popcll(tak1);
+          if (!direct) {
+            if (lane < WMAX) S.tmask[lane] = 0ull;
+            wsync();
+          }
+#pragma unroll
+          for (int h = 0; h < NH; ++h) {
+            const uint64_t th = h == 0 ? tak0 : tak1;
+            if ((th >> lane) & 1ull) {
+              const int u = uu[h];
+              if (direct) {
+                const int q = (h == 0 ? 0 : __popcll(tak0)) + __popcll(th & ltm);
+                tlu[q] = (uint16_t)u;
+                tlv[q] = S.scurv[sp + u - S.wlo - S.sbase];
+              } else {
+                atomicOr((unsigned long long*)&S.tmask[u >> 6], 1ull << (u & 63));
+              }
+            }
+          }
+          wsync();
+        };
+        if (nc <= 64) run(std::integral_constant<int, 1>{});
+        else run(std::integral_constant<int, 2>{});
+        return true;
+      };
+      // Member-indexed form (more than 128 candidates, or FBR_FEAT_COMPACT=0): its und / tak
+      // words live only inside this lambda.
+      auto corner_generic = [&]() __attribute__((always_inline)) {
+        uint64_t und[WMAX], tak[WMAX];
 #pragma unroll
         for (int w = 0; w < WMAX; ++w) {
           const int u = 64 * w + lane;
@@ -933,22 +1118,35 @@ k_features(FeatArgs a) {
 #ifndef FBR_FEAT_SKIP_CORNER
         greedy_rounds(m, lane, und, tak, [&](int u) { return S.cm[u] & 1023u; }, a, job);
 #endif
+        T = 0;
+        ccode = 2;
+        if (direct) {
+#pragma unroll
+          for (int w = 0; w < WMAX; ++w) {
+            if ((tak[w] >> lane) & 1ull) {
+              const int q = T + __popcll(tak[w] & ltm);
+              const int u = 64 * w + lane;
+              tlu[q] = (uint16_t)u;
+              tlv[q] = S.scurv[sp + u - S.wlo - S.sbase];
+            }
+            T += __popcll(tak[w]);
+          }
+        }
+        if (lane < WMAX) {
+          uint64_t t = 0;
+#pragma unroll
+          for (int w = 0; w < WMAX; ++w)
+            if (w == lane) t = tak[w];
+          S.tmask[lane] = t;
+        }
+        wsync();
+      };
+      auto corner_walk = [&]() __attribute__((always_inline)) {
+        if (!(a.compact && corner_compact())) corner_generic();
       };
       corner_walk();
       FBR_STAMP(4);
-      int T = 0;
       if (direct) {  // visit order of the taken corners: ep first, then descending curvature
-#pragma unroll
-        for (int w = 0; w < WMAX; ++w) {
-          if ((tak[w] >> lane) & 1ull) {
-            const int q = T + __popcll(tak[w] & ((1ull << lane) - 1ull));
-            const int u = 64 * w + lane;
-            tlu[q] = (uint16_t)u;
-            tlv[q] = S.scurv[sp + u - S.wlo - S.sbase];
-          }
-          T += __popcll(tak[w]);
-        }
-        wsync();
         bool tf = false;
         for (int c = lane; c < T; c += 64) {
           const int u = tlu[c];
@@ -974,14 +1172,6 @@ k_features(FeatArgs a) {
         wsync();
         FBR_STAMP(11);
       }
-      if (lane < WMAX) {
-        uint64_t t = 0;
-#pragma unroll
-        for (int w = 0; w < WMAX; ++w)
-          if (w == lane) t = tak[w];
-        S.tmask[lane] = t;
-      }
-      wsync();
       // the first kCornerPerSeg taken corners in visit order are kept (the walk breaks there)
       const int R = direct ? T : m + 1;
       int taken = 0;
@@ -989,7 +1179,7 @@ k_features(FeatArgs a) {
         const int rr = r0 + lane;
         int u = -1;
         if (rr < R) u = direct ? (int)vis[rr] : (int)S.sorder[rr == 0 ? m : m - rr];
-        const bool acc = u >= 0 && ((S.tmask[u >> 6] >> (u & 63)) & 1ull);
+        const bool acc = u >= 0 && (direct || ((S.tmask[u >> 6] >> (u & 63)) & 1ull));  // vis holds taken ones only
         const uint64_t mk = __ballot(acc);
         const int pos = taken + __popcll(mk & ((1ull << lane) - 1ull));
         if (acc && pos < kCornerPerSeg) {
@@ -1012,31 +1202,39 @@ k_features(FeatArgs a) {
       // if a member within reach of ep stays undecided (its chain of higher-priority conflicts
       // leaves the window), the whole walk runs.
       const bool bnd = !seg_full;
-      const int ulo = bnd ? max(0, m - (kSurfWindow - 1)) : 0;
-      auto surf_cand = [&](bool window) __attribute__((always_inline)) {
-#pragma unroll
-        for (int w = 0; w < WMAX; ++w) {
-          const int u = 64 * w + lane;
-          bool cand = false;
-          if (u <= m && (!window || u >= ulo - 5)) {
-            const int li = sp + u - S.wlo;
-            cand = !S.picked.get(li) && S.surfc.get(li);
-          }
-          und[w] = __ballot(cand);
-          tak[w] = 0ull;
-        }
-      };
+      const int ulo = bnd ? max(0, m - (swin - 1)) : 0;
       auto surf_cm = [&](int u) {
         const uint32_t c = S.cm[u];
         return ((c >> 10) & 1023u) & ~(c & 1023u);
       };
-      if (bnd && j == lastj) {  // the ring's last segment: no surf pick of it is observable
+      auto surf_apply = [&](int u) __attribute__((always_inline)) {
+        const int li = sp + u - S.wlo;
+        const uint32_t c = S.cm[u];
+        atomicOr((unsigned long long*)&S.labneg.w[li >> 6], 1ull << (li & 63));
+        or_range(S.picked, li - (int)((c >> 24) & 15u), li + (int)((c >> 20) & 15u));
+      };
+      // Member-indexed form.  window: resolve [ulo, m] first (FBR_FEAT_COMPACT=0); rest: the
+      // whole walk follows a window that cm was computed for only.  Returns the path record code.
+      auto surf_generic = [&](bool window, bool rest) __attribute__((always_inline)) -> int {
+        uint64_t und[WMAX], tak[WMAX];
+        auto surf_cand = [&](bool win) __attribute__((always_inline)) {
 #pragma unroll
-        for (int w = 0; w < WMAX; ++w) tak[w] = 0ull;
-      } else {
-        surf_cand(bnd && ulo > 0);
+          for (int w = 0; w < WMAX; ++w) {
+            const int u = 64 * w + lane;
+            bool cand = false;
+            if (u <= m && (!win || u >= ulo - 5)) {
+              const int li = sp + u - S.wlo;
+              cand = !S.picked.get(li) && S.surfc.get(li);
+            }
+            und[w] = __ballot(cand);
+            tak[w] = 0ull;
+          }
+        };
+        int code = rest ? 2 : 3;
+        bool whole = true;
 #ifndef FBR_FEAT_SKIP_SURF
-        if (bnd && ulo > 0) {
+        if (window) {
+          surf_cand(true);
           uint64_t frz[WMAX];
 #pragma unroll
           for (int w = 0; w < WMAX; ++w) {
@@ -1051,32 +1249,81 @@ k_features(FeatArgs a) {
             const int u = 64 * w + lane;
             open |= u >= m - 4 && u <= m && ((und[w] >> lane) & 1ull) && !((frz[w] >> lane) & 1ull);
           }
-          if (__any(open)) {
-            if (direct) {  // cm was computed for the listed members only: all of them now
-              bool tf2 = false;
-              for (int u = lane; u <= m; u += 64) tf2 |= cm_member(u);
-              wsync();
-              if (__any(tf2)) sorted_order();  // a relevant tie: introsort's order for the whole walk
-            }
-            surf_cand(false);
-            greedy_rounds(m, lane, und, tak, surf_cm, a, job);
+          whole = __any(open);
+          code = whole ? 2 : 1;
+          rest = whole;
+        }
+        if (whole) {
+          if (rest && direct) {  // cm was computed for the listed members only: all of them now
+            bool tf2 = false;
+            for (int u = lane; u <= m; u += 64) tf2 |= cm_member(u);
+            wsync();
+            if (__any(tf2)) sorted_order();  // a relevant tie: introsort's order for the whole walk
           }
-        } else {
+          surf_cand(false);
           greedy_rounds(m, lane, und, tak, surf_cm, a, job);
         }
+#else
+        surf_cand(false);
 #endif
-      }
-      FBR_STAMP(6);
+        FBR_STAMP(6);
 #pragma unroll
-      for (int w = 0; w < WMAX; ++w) {
-        const int u = 64 * w + lane;
-        if (u <= m && ((tak[w] >> lane) & 1ull)) {
-          const int li = sp + u - S.wlo;
-          const uint32_t c = S.cm[u];
-          atomicOr((unsigned long long*)&S.labneg.w[li >> 6], 1ull << (li & 63));
-          or_range(S.picked, li - (int)((c >> 24) & 15u), li + (int)((c >> 20) & 15u));
+        for (int w = 0; w < WMAX; ++w) {
+          const int u = 64 * w + lane;
+          if (u <= m && ((tak[w] >> lane) & 1ull)) surf_apply(u);
         }
+        return code;
+      };
+      // Compact form of the batch walk: the window and the <= 5 frozen candidates left of it,
+      // re-based at member ulo - 5, are at most swin + 5 <= 69 bits: lane l owns members base + l
+      // and (lanes 0..4) base + 64 + l, and the 10 member-offset bits of surf_cm are the position
+      // bits as they stand.  Returns false (nothing applied) when a member within reach of ep stays
+      // undecided.
+      auto surf_compact = [&]() __attribute__((always_inline)) -> bool {
+        const int base = max(0, ulo - 5);
+        const bool two = m - base >= 64;
+        const int u0 = base + lane, u1 = base + 64 + lane;
+        const int lb = li0 + base, wb = (lb >> 6) + lane;
+        const uint64_t swv = (lane < 3 && wb < S.nw) ? ~S.picked.w[wb] & S.surfc.w[wb] : 0ull;
+        uint64_t und0 = member_bits(swv, lb & 63, 0, m - base);
+        uint64_t und1 = two ? member_bits(swv, lb & 63, 1, m - base) : 0ull;
+        const uint64_t frz0 = und0 & ((1ull << (ulo - base)) - 1ull);
+        uint64_t tak0 = 0ull, tak1 = 0ull;
+        auto rel_of = [&](int u) __attribute__((always_inline)) {
+          const uint32_t s10 = surf_cm(u);
+          return (s10 & 31u) | ((s10 >> 5) << 6);
+        };
+#ifndef FBR_FEAT_SKIP_SURF
+        const bool live0 = ((und0 & ~frz0) >> lane) & 1ull;
+        if (!two) {
+          U128 cf[1];
+          cf[0] = place11(live0 ? rel_of(u0) : 0u, lane);
+          compact_rounds<1>(lane, und0, und1, tak0, tak1, cf, frz0, 4 * (m - base + 2), a, job);
+        } else {
+          U128 cf[2];
+          cf[0] = place11(live0 ? rel_of(u0) : 0u, lane);
+          cf[1] = place11(((und1 >> lane) & 1ull) ? rel_of(u1) : 0u, 64 + lane);
+          compact_rounds<2>(lane, und0, und1, tak0, tak1, cf, frz0, 4 * (m - base + 2), a, job);
+        }
+        // every candidate within reach of ep decided?
+        const bool open = (u0 >= m - 4 && u0 <= m && (((und0 & ~frz0) >> lane) & 1ull)) ||
+                          (u1 >= m - 4 && u1 <= m && ((und1 >> lane) & 1ull));
+        if (__any(open)) return false;
+#endif
+        FBR_STAMP(6);
+        if ((tak0 >> lane) & 1ull) surf_apply(u0);
+        if ((tak1 >> lane) & 1ull) surf_apply(u1);
+        return true;
+      };
+      int scode = 0;
+      if (bnd && j == lastj) {  // the ring's last segment: no surf pick of it is observable
+        FBR_STAMP(6);
+      } else if (bnd && a.compact) {
+        scode = surf_compact() ? 1 : surf_generic(false, ulo > 0);
+      } else {
+        scode = surf_generic(bnd && ulo > 0, false);
       }
+      rec |= (uint32_t)(ccode | (scode << 2)) << (4 * j);
       pf_seg = pf_next;
       if (pf_seg >= 0) {
 #pragma unroll
@@ -1103,6 +1350,7 @@ k_features(FeatArgs a) {
   }
   if (cb <= 0 && tid < 5 && tid < S.L) st->picked04[tid] = S.picked.get(tid) ? 1 : 0;
   if (tid == 0) a.corner_cnt[slot] = corner_cnt;
+  if (tid == 0 && a.paths) a.paths[slot] = rec;
 #ifdef FBR_FEAT_STAMPS
   FBR_STAMP(9);
   if (tid == 0 && a.stamps)

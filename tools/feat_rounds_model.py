@@ -3,7 +3,9 @@
 before touching the kernel.  For C2 scans: the oracle's projection, then per segment the corner
 and surf candidates, the conflict structure (+-5 reach stopped by column gaps > 10) and the
 number of rounds the wave needs (corner walk over the whole segment; batch surf walk over the
-window [m-63, m] with the candidates left of it frozen).
+window [m-63, m] with the candidates left of it frozen).  Also the sizes the compact walks run
+at: the share of segments with <= 64, <= 128 and more corner candidates, and how often a surf
+window of 59 or 64 members leaves a member within reach of ep undecided (the whole-walk fall-back).
 usage: feat_rounds_model.py [scans]
 """
 import os
@@ -45,11 +47,32 @@ def rounds(cand, prio, nbrs):
     return r, len(tak)
 
 
+def window_falls_back(cand, prio, nbrs, m, win):
+    """The batch surf window [m - win + 1, m] with the candidates of the 5 members left of it frozen:
+    does a candidate within reach of ep (members m - 4 .. m) stay undecided?"""
+    ulo = max(0, m - (win - 1))
+    if ulo == 0:
+        return False
+    und = set(u for u in np.flatnonzero(cand).tolist() if u >= ulo - 5)
+    frz = set(u for u in und if u < ulo)
+    tak = set()
+    while True:
+        live = und - frz
+        new_t = [u for u in live if not any(prio[v] > prio[u] and (v in tak or v in und) for v in nbrs[u])]
+        tak |= set(new_t)
+        new_n = [u for u in live if u not in tak and any(prio[v] > prio[u] and v in tak for v in nbrs[u])]
+        if not new_t and not new_n:
+            break
+        und -= set(new_t) | set(new_n)
+    return any(u >= m - 4 for u in und - frz)
+
+
 def main():
     ns = int(sys.argv[1]) if len(sys.argv) > 1 else 2
     P = synth.config_params("C2")
     H = P.n_scan
     stats = {"corner": [], "surf": [], "ccand": [], "scand": [], "m": []}
+    fb = {59: [], 64: []}
     for pts, _, _ in synth.make_jobs("C2", ns, base_seed=1000):
         pr = O.project(P, pts)
         r = pr["range"].astype(np.float32)
@@ -91,6 +114,8 @@ def main():
                 win = sc.copy()
                 win[:max(0, lo - 5)] = False
                 rs, _ = rounds(win, ps, nb)
+                for w in fb:
+                    fb[w].append(window_falls_back(sc, ps, nb, m, w))
                 stats["corner"].append(rc)
                 stats["surf"].append(rs)
                 stats["ccand"].append(int(cc.sum()))
@@ -99,6 +124,11 @@ def main():
     for k, v in stats.items():
         v = np.array(v)
         print(f"{k:6s} mean {v.mean():7.2f}  p50 {np.median(v):6.1f}  p90 {np.percentile(v, 90):6.1f}  max {v.max()}")
+    cc = np.array(stats["ccand"])
+    print(f"segments {len(cc)}: corner candidates <= 64: {100 * (cc <= 64).mean():.1f} %, 65..128: "
+          f"{100 * ((cc > 64) & (cc <= 128)).mean():.1f} %, > 128: {100 * (cc > 128).mean():.1f} %")
+    for w, v in fb.items():
+        print(f"surf window {w}: whole-walk fall-back in {100 * np.mean(v):.2f} % of the segments")
 
 
 if __name__ == "__main__":
