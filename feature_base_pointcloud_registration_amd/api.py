@@ -15,8 +15,8 @@ import os
 
 import numpy as np
 
-from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrParams,
-                        FbrRegStats, PointCloud2, default_params, ptr)
+from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
+                        FbrLoopResult, FbrParams, FbrRegStats, PointCloud2, default_params, icp_params, loop_params, ptr)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "fbr_imu_convert", "fbr_imu_deskew_info", "fbr_set_deskew", "fbr_stream_copy_bandwidth", "fbr_valu_peak",
     "fbr_keyframe_params_default", "fbr_keyframes_add", "fbr_keyframes_set_pose", "fbr_keyframes_count",
     "fbr_keyframes_reset", "fbr_extract_surrounding_keyframes",
+    "fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align", "fbr_selftest_nn1",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -120,6 +121,11 @@ def lib():
             "fbr_keyframes_count": (ctypes.c_int, [_VP, _VP]),
             "fbr_keyframes_reset": (ctypes.c_int, [_VP]),
             "fbr_extract_surrounding_keyframes": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP, _VP]),
+            "fbr_loop_params_default": (None, [_VP]),
+            "fbr_detect_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP]),
+            "fbr_perform_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP]),
+            "fbr_icp_align": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP]),
+            "fbr_selftest_nn1": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, ctypes.c_float, _VP, _VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
             "fbr_comm_create_local": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int]),
@@ -509,6 +515,47 @@ class Context:
                                                        ctypes.byref(nc), ctypes.byref(ns), ctypes.byref(nf)),
                "fbr_extract_surrounding_keyframes")
         return nc.value, ns.value, nf.value
+
+    # ---- loop closure (mapOptmization.h:606-782) ----
+    def detect_loop_closure(self, stamp, lparams=None):
+        """detectLoopClosure at timeLaserCloudInfoLast = stamp: (latest_id, closest_id), or None when
+        there is no candidate."""
+        lp = lparams if lparams is not None else loop_params()
+        a, b = _I32(), _I32()
+        _check(lib().fbr_detect_loop_closure(self._h, ctypes.c_double(stamp), ctypes.byref(lp), ctypes.byref(a),
+                                             ctypes.byref(b)), "fbr_detect_loop_closure")
+        return None if a.value < 0 else (a.value, b.value)
+
+    def perform_loop_closure(self, stamp, lparams=None, raw=False):
+        """performLoopClosure up to the between-factor: the fbr_loop_result as a dict (raw: the
+        FbrLoopResult structure itself)."""
+        lp = lparams if lparams is not None else loop_params()
+        r = FbrLoopResult()
+        _check(lib().fbr_perform_loop_closure(self._h, ctypes.c_double(stamp), ctypes.byref(lp), ctypes.byref(r)),
+               "fbr_perform_loop_closure")
+        return r if raw else r.as_dict()
+
+    def icp_align(self, source, target, iparams=None, raw=False):
+        """The loop closure's ICP on two host clouds: the fbr_icp_result as a dict."""
+        ip = iparams if iparams is not None else icp_params()
+        source = _as_points(source, POINT_XYZI)
+        target = _as_points(target, POINT_XYZI)
+        r = FbrIcpResult()
+        _check(lib().fbr_icp_align(self._h, ptr(source) if len(source) else None, len(source),
+                                   ptr(target) if len(target) else None, len(target), ctypes.byref(ip),
+                                   ctypes.byref(r)), "fbr_icp_align")
+        return r if raw else r.as_dict()
+
+    def selftest_nn1(self, target, query, max_distance):
+        """The ICP correspondence search alone: (index int32 [n_query], -1 = none; d2 float32)."""
+        target = _as_points(target, POINT_XYZI)
+        query = _as_points(query, POINT_XYZI)
+        idx = np.zeros(max(len(query), 1), np.int32)
+        d2 = np.zeros(max(len(query), 1), np.float32)
+        _check(lib().fbr_selftest_nn1(self._h, ptr(target) if len(target) else None, len(target),
+                                      ptr(query) if len(query) else None, len(query), ctypes.c_float(max_distance),
+                                      ptr(idx), ptr(d2)), "fbr_selftest_nn1")
+        return idx[:len(query)].copy(), d2[:len(query)].copy()
 
     @property
     def stream_handle(self):

@@ -397,4 +397,38 @@ struct KfSeg {               // one selected keyframe cloud: pool[src .. src+cou
 };
 void launch_kf_transform(hipStream_t s, const float4* pool, const KfSeg* segs, int nseg, int64_t max_count, float4* out);
 
+// ---- loop closure ICP (k_icp.hip) ----
+struct IcpState {
+  float T[12];        // the last iteration's transform, row-major 3x4
+  float fin[12];      // final_transformation_
+  double prev_mse;    // correspondences_prev_mse_
+  int32_t stopped;    // the loop has ended: iteration kernels already enqueued return at once
+  int32_t converged, convergence, iterations, ncorr;
+  int32_t pad[3];
+};
+constexpr int kIcpSums = 18;  // doubles per workgroup partial (17 used)
+struct IcpArgs {
+  const float4* src;   // [n] the source cloud
+  float4* x;           // [n] the source under the transforms so far (the searched queries)
+  int64_t n;
+  const float4* tgt;   // [nt] the target in index order
+  int64_t nt;
+  MapGrid grid;        // dense grid over the target (grid_build_device), cubic cells
+  int use_grid;        // 0: every query goes to the brute-force kernel
+  double gate2;        // max_correspondence_distance^2 (infinity: none)
+  unsigned long long* key;  // [n] (d2 bits << 32) | target index, ~0 = none
+  int32_t* far_list;   // [n] queries left to the brute-force kernel
+  int32_t* far_cnt;    // [1]
+  double* partial;     // [ceil(n / 256)][kIcpSums]
+  IcpState* st;
+  unsigned long long* flag;  // host-mapped: (generation << 32) | iterations << 1 | stopped; may be null
+};
+void launch_icp_init(hipStream_t s, const IcpArgs& a);
+// mode 0: an iteration's search (first = 1: X = source, else X = T X); mode 1: the fitness pass
+// (X = final * source; the caller passes gate2 = infinity)
+void launch_icp_nn(hipStream_t s, const IcpArgs& a, int mode, int first);
+void launch_icp_far(hipStream_t s, const IcpArgs& a, int mode);
+void launch_icp_solve(hipStream_t s, const IcpArgs& a, int max_iter, double teps, double feps, unsigned long long gen);
+void launch_icp_finish(hipStream_t s, const IcpArgs& a, fbr_icp_result* out);
+
 }  // namespace fbr

@@ -54,6 +54,66 @@ def keyframe_params(**kw):
     return p
 
 
+# loop closure (include/fbr.h "loop closure")
+FBR_ICP_NOT_CONVERGED, FBR_ICP_ITERATIONS, FBR_ICP_TRANSFORM, FBR_ICP_ABS_MSE, FBR_ICP_REL_MSE, \
+    FBR_ICP_NO_CORRESPONDENCES = range(6)
+FBR_LOOP_CLOSED, FBR_LOOP_NO_CANDIDATE, FBR_LOOP_NOT_CONVERGED, FBR_LOOP_REJECTED_FITNESS = range(4)
+
+
+class _Dictable(ctypes.Structure):
+    def as_dict(self):
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            if isinstance(v, ctypes.Array):
+                v = np.array(v[:], np.float32)
+            elif isinstance(v, _Dictable):
+                v = v.as_dict()
+            out[name] = v
+        return out
+
+
+class FbrIcpParams(_Dictable):
+    _fields_ = [("max_correspondence_distance", ctypes.c_float), ("max_iterations", ctypes.c_int32),
+                ("transformation_epsilon", ctypes.c_double), ("euclidean_fitness_epsilon", ctypes.c_double)]
+
+
+class FbrLoopParams(_Dictable):
+    _fields_ = [("search_radius", ctypes.c_float), ("search_time_diff", ctypes.c_float),
+                ("search_num", ctypes.c_int32), ("fitness_score", ctypes.c_float),
+                ("icp_leaf_size", ctypes.c_float), ("icp", FbrIcpParams)]
+
+
+class FbrIcpResult(_Dictable):
+    _fields_ = [("converged", ctypes.c_int32), ("convergence", ctypes.c_int32), ("iterations", ctypes.c_int32),
+                ("n_correspondences", ctypes.c_int32), ("fitness", ctypes.c_double),
+                ("transform", ctypes.c_float * 16)]
+
+
+class FbrLoopResult(_Dictable):
+    _fields_ = [("status", ctypes.c_int32), ("latest_id", ctypes.c_int32), ("closest_id", ctypes.c_int32),
+                ("n_source", ctypes.c_int32), ("n_target", ctypes.c_int32), ("icp", FbrIcpResult),
+                ("pose_corrected", ctypes.c_float * 6), ("pose_closest", ctypes.c_float * 6),
+                ("between", ctypes.c_float * 16)]
+
+
+def icp_params(**kw):
+    """performLoopClosure's "ICP Settings" (mapOptmization.h:689-694)."""
+    p = FbrIcpParams(100.0, 100, 1e-6, 1e-6)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def loop_params(icp=None, **kw):
+    """fbr_loop_params_default (params.yaml:72-75 and the ICP settings); `icp`: dict of
+    fbr_icp_params overrides."""
+    p = FbrLoopParams(15.0, 30.0, 25, 0.3, 0.0, icp_params(**(icp or {})))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

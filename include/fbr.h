@@ -304,6 +304,112 @@ int fbr_keyframes_reset(fbr_ctx* ctx);
 int fbr_extract_surrounding_keyframes(fbr_ctx* ctx, double stamp, const fbr_keyframe_params* kp,
                                       int64_t* n_corner_map, int64_t* n_surf_map, int32_t* n_frames);
 
+/* ---- loop closure (detectLoopClosure / performLoopClosure, mapOptmization.h:606-782) -----------
+ * The candidate search runs on the host over the key poses; the clouds, their VoxelGrid and the
+ * ICP stay in HBM (the keyframe clouds fbr_keyframes_add stored: no cloud crosses PCIe).  GTSAM
+ * stays with the caller: fbr_perform_loop_closure returns the between-factor to add, the caller
+ * runs its pose graph and rewrites the key poses with fbr_keyframes_set_pose.  The loop calls
+ * change no key pose and touch neither the registration map, its grids nor a keyframe local map.
+ *
+ * detectLoopClosure (:606-674) at timeLaserCloudInfoLast = `stamp`:
+ *   - radius search around the last key pose with fbr_extract_surrounding_keyframes' conventions:
+ *     d2 = ((dx dx + dy dy) + dz dz) in float, accepted when d2 < r^2, ascending d2, ties by index;
+ *   - the candidate is the first hit with |time - stamp| > search_time_diff: the nearest
+ *     old-enough keyframe (the reference's comment says the oldest; its code takes the nearest);
+ *   - no candidate when no hit qualifies or the candidate is the last keyframe itself;
+ *   - source: the last keyframe's corner cloud, then its surf cloud, transformed by its stored pose;
+ *   - target: keyframes closest - search_num .. closest + search_num (indices < 0 or > latest
+ *     skipped), each its corner then its surf cloud under its stored pose, concatenated in that
+ *     order, then one VoxelGrid at icp_leaf_size.
+ *
+ * ICP: pcl::IterativeClosestPoint with TransformationEstimationSVD and DefaultConvergenceCriteria,
+ * no rejectors, guess = identity, restated (not pinned against PCL itself, like the oracle):
+ *   X = source; final = I; prev_mse = DBL_MAX; it = 0
+ *   loop:
+ *     for each X[i]: j = nearest target point, d2 = ((dx dx + dy dy) + dz dz) in float, ties to
+ *          the lowest target index; a correspondence iff d2 <= max_correspondence_distance^2
+ *          (the square taken in double); non-finite points have none
+ *     fewer than 3 correspondences: converged = 0, FBR_ICP_NO_CORRESPONDENCES, stop
+ *     T = Umeyama without scaling over the correspondences in double (means, sigma = sum (t - mt)
+ *         (s - ms)^T / n, SVD, S = diag(1, 1, det(sigma) < 0 ? -1 : 1), R = U S V^T,
+ *         t = mt - R ms), rounded to float
+ *     X[i] = T X[i] in float, rows ((r0 x + r1 y) + r2 z) + t; final = T final in float; ++it
+ *     it >= max_iterations: converged = 1, FBR_ICP_ITERATIONS, stop
+ *     cos = 0.5 (T00 + T11 + T22 - 1), t2 = |t|^2 in double; cos >= 1 - transformation_epsilon and
+ *         t2 <= transformation_epsilon: converged = 1, FBR_ICP_TRANSFORM, stop
+ *     mse = mean d2 of the correspondences (double); |mse - prev_mse| < 1e-12: FBR_ICP_ABS_MSE,
+ *         stop; |mse - prev_mse| / prev_mse < euclidean_fitness_epsilon: FBR_ICP_REL_MSE, stop
+ *         (both converged = 1); prev_mse = mse
+ *   fitness = mean over the source points of the d2 of final * source[i] to its nearest target
+ *         point (no distance gate; DBL_MAX when no point has one)
+ * Two calls on the same input return the same bytes. */
+typedef struct fbr_icp_params {        /* performLoopClosure's "ICP Settings", :689-694 */
+  float   max_correspondence_distance; /* 100                                          */
+  int32_t max_iterations;              /* 100                                          */
+  double  transformation_epsilon;      /* 1e-6                                         */
+  double  euclidean_fitness_epsilon;   /* 1e-6                                         */
+} fbr_icp_params;
+
+typedef struct fbr_loop_params {
+  float   search_radius;      /* historyKeyframeSearchRadius   15   params.yaml:72 */
+  float   search_time_diff;   /* historyKeyframeSearchTimeDiff 30 s params.yaml:73 */
+  int32_t search_num;         /* historyKeyframeSearchNum      25   params.yaml:74 */
+  float   fitness_score;      /* historyKeyframeFitnessScore   0.3  params.yaml:75 */
+  float   icp_leaf_size;      /* downSizeFilterICP leaf; 0 = the ctx's mapping_surf_leaf_size (:192) */
+  fbr_icp_params icp;
+} fbr_loop_params;
+
+/* fbr_icp_result.convergence */
+#define FBR_ICP_NOT_CONVERGED 0
+#define FBR_ICP_ITERATIONS 1
+#define FBR_ICP_TRANSFORM 2
+#define FBR_ICP_ABS_MSE 3
+#define FBR_ICP_REL_MSE 4
+#define FBR_ICP_NO_CORRESPONDENCES 5
+
+typedef struct fbr_icp_result {
+  int32_t converged;          /* icp.hasConverged()                                      */
+  int32_t convergence;        /* FBR_ICP_*                                               */
+  int32_t iterations;         /* nr_iterations_                                          */
+  int32_t n_correspondences;  /* of the last iteration                                   */
+  double  fitness;            /* icp.getFitnessScore()                                   */
+  float   transform[16];      /* icp.getFinalTransformation(), row-major                 */
+} fbr_icp_result;
+
+/* fbr_loop_result.status */
+#define FBR_LOOP_CLOSED 0
+#define FBR_LOOP_NO_CANDIDATE 1      /* detectLoopClosure returned false                  */
+#define FBR_LOOP_NOT_CONVERGED 2     /* :715 first half                                   */
+#define FBR_LOOP_REJECTED_FITNESS 3  /* :715 second half                                  */
+
+typedef struct fbr_loop_result {
+  int32_t status;
+  int32_t latest_id, closest_id;     /* -1 when there is no candidate                     */
+  int32_t n_source, n_target;        /* latestKeyFrameCloud / DS'd nearHistoryKeyFrameCloud sizes */
+  fbr_icp_result icp;
+  float   pose_corrected[6];         /* tCorrect = correction * tWrong (:739-741), [r,p,y,x,y,z] */
+  float   pose_closest[6];           /* poseTo (:744)                                     */
+  float   between[16];               /* poseFrom.between(poseTo) = tCorrect^-1 * tClosest, row-major, computed in double */
+} fbr_loop_result;
+
+void fbr_loop_params_default(fbr_loop_params* p);
+/* detectLoopClosure alone: FBR_OK with both ids -1 when there is no candidate (no keyframes
+ * included). */
+int fbr_detect_loop_closure(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, int32_t* latest_id,
+                            int32_t* closest_id);
+/* performLoopClosure up to the factor (:676-758).  With FBR_LOOP_NO_CANDIDATE the ids are -1 and the
+ * remaining fields zero; otherwise every field is filled, whatever the status (pose_corrected and
+ * between are what the reference would have used had it accepted the match). */
+int fbr_perform_loop_closure(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, fbr_loop_result* out);
+/* The ICP above on two host clouds (the search grid's cells follow the ctx's mapping_surf_leaf_size). */
+int fbr_icp_align(fbr_ctx* ctx, const fbr_point_xyzi* source, int64_t n_source, const fbr_point_xyzi* target,
+                  int64_t n_target, const fbr_icp_params* ip, fbr_icp_result* out);
+/* Diagnostic: the ICP correspondence search alone (tests compare with a brute-force host search).
+ * index[i] = the nearest target point of query[i] with d2 <= max_distance^2, d2[i] its float squared
+ * distance; index -1 (and d2 = FLT_MAX) when there is none. */
+int fbr_selftest_nn1(fbr_ctx* ctx, const fbr_point_xyzi* target, int64_t n_target, const fbr_point_xyzi* query,
+                     int64_t n_query, float max_distance, int32_t* index, float* d2);
+
 /* Down-sampled global map actually used (sizes, then optional copies; pass NULL to skip).  After
  * fbr_extract_surrounding_keyframes: the keyframe local map (laserCloud{Corner,Surf}FromMapDS). */
 int fbr_get_map(fbr_ctx* ctx, int64_t* n_corner, int64_t* n_surf, fbr_point_xyzi* corner,

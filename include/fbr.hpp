@@ -288,6 +288,31 @@ class MapOptimization {
           "fbr_extract_surrounding_keyframes");
   }
 
+  /* Loop closure (mapOptmization.h:606-782).  detectLoopClosure returns false when there is no
+   * candidate; performLoopClosure runs the ICP on the device and returns the fbr_loop_result: with
+   * status FBR_LOOP_CLOSED the caller adds BetweenFactor(latest_id, closest_id, between,
+   * Variances(icp.fitness)) to its graph and writes the optimised poses back with correctPose. */
+  bool detectLoopClosure(double timeLaserCloudInfoLast, const fbr_loop_params& lp, int* latestID, int* closestID) {
+    int32_t a = -1, b = -1;
+    check(fbr_detect_loop_closure(c_.get(), timeLaserCloudInfoLast, &lp, &a, &b), "fbr_detect_loop_closure");
+    if (latestID) *latestID = a;
+    if (closestID) *closestID = b;
+    return a >= 0;
+  }
+  fbr_loop_result performLoopClosure(double timeLaserCloudInfoLast, const fbr_loop_params& lp) {
+    fbr_loop_result r{};
+    check(fbr_perform_loop_closure(c_.get(), timeLaserCloudInfoLast, &lp, &r), "fbr_perform_loop_closure");
+    return r;
+  }
+  /* pcl::IterativeClosestPoint::align + getFitnessScore on two host clouds. */
+  fbr_icp_result icpAlign(const std::vector<fbr_point_xyzi>& source, const std::vector<fbr_point_xyzi>& target,
+                          const fbr_icp_params& ip) {
+    fbr_icp_result r{};
+    check(fbr_icp_align(c_.get(), source.data(), (int64_t)source.size(), target.data(), (int64_t)target.size(), &ip, &r),
+          "fbr_icp_align");
+    return r;
+  }
+
  private:
   Context& c_;
   double timeLastProcessing_ = -1.0;  // mapOptmization.h:135 (timeLastProcessing = -1)

@@ -1,0 +1,335 @@
+"""Loop closure (detectLoopClosure / performLoopClosure, mapOptmization.h:606-782): the keyframe
+candidate search, the ICP between the latest keyframe and the candidate's neighbourhood on the
+device, and the between-factor handed back to the caller's pose graph, checked against the NumPy
+restatement of the header's contract (tests/loop_model.py).
+
+Bars:
+  * fbr_selftest_nn1: indices equal and d2 bit-equal to the float32 brute force;
+  * the loop call on the out-and-back fixture: candidate, cloud sizes, iteration count and
+    convergence state equal to the model's; corrected pose within 1e-4 m / 1e-4 rad of the model's;
+    fitness within relative 1e-5 of the model's fitness at the device's own transform; `between`
+    within 1e-5 of tCorrect^-1 tClosest recomputed in float64; a second call byte-identical; the
+    registration map untouched.
+The fixture context runs with exact_voxel_order = 1, so the device's down-sampled target has the
+oracle's bits and the model and the device align the same clouds.
+"""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import loop_model as M
+import pyoracle as O
+from feature_base_pointcloud_registration_amd import api, synth
+from feature_base_pointcloud_registration_amd.fbr_types import (FBR_ICP_ITERATIONS, FBR_ICP_NO_CORRESPONDENCES,
+                                                                FBR_ICP_TRANSFORM, FBR_LOOP_CLOSED,
+                                                                FBR_LOOP_NO_CANDIDATE, FBR_LOOP_NOT_CONVERGED,
+                                                                FBR_LOOP_REJECTED_FITNESS, KEYPOSE, POINT_XYZI,
+                                                                FbrLoopParams, default_params, icp_params,
+                                                                loop_params)
+
+POSE_TOL = 1e-4
+STAMP = 38.5
+N_KF = 20
+DRIFT = dict(yaw=0.03, x=0.35, y=-0.25, z=0.1)
+
+
+# ---- CPU ------------------------------------------------------------------------------------------
+def test_loop_params_default_matches_params_yaml():
+    p = FbrLoopParams()
+    api.lib().fbr_loop_params_default(ctypes.byref(p))
+    q = loop_params()
+    assert p.as_dict() == q.as_dict()
+    assert (p.search_radius, p.search_time_diff, p.search_num, p.fitness_score) == (15.0, 30.0, 25, np.float32(0.3))
+    assert p.icp_leaf_size == 0.0
+    i = p.icp
+    assert (i.max_correspondence_distance, i.max_iterations, i.transformation_epsilon,
+            i.euclidean_fitness_epsilon) == (100.0, 100, 1e-6, 1e-6)
+
+
+def test_loop_symbols_are_exported():
+    lib = ctypes.CDLL(api.lib_path())
+    for name in ("fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align",
+                 "fbr_selftest_nn1"):
+        assert hasattr(lib, name), name
+        assert name in api.EXPORTED_SYMBOLS
+    assert ctypes.sizeof(FbrLoopParams) == 48
+
+
+def gt_pose(k):
+    s = k if k < 10 else 19 - k
+    return np.array([0.0, 0.0, 0.02 * s, 1.5 * s, 0.3 * np.sin(0.5 * s) + (0.4 if k >= 10 else 0.0), 0.0])
+
+
+@functools.lru_cache(maxsize=None)
+def fixture():
+    """The out-and-back run: 20 keyframes driving 13.5 m out and back beside the outward track, the
+    last one's stored pose drifted; search_num = 3, stamp = 38.5.  Returns (P, stored poses, corner
+    clouds, surf clouds, loop params, the model's result)."""
+    P = default_params(16, 1800, exact_voxel_order=1)
+    poses = np.zeros(N_KF, KEYPOSE)
+    corners, surfs = [], []
+    for k in range(N_KF):
+        gt = gt_pose(k)
+        f = O.Stream(P).features(synth.scan(gt, 16, 1800, seed=100 + k))
+        corners.append(O.voxel_grid(f["corner"], P.mapping_corner_leaf_size))
+        surfs.append(O.voxel_grid(f["surf"], P.mapping_surf_leaf_size))
+        poses[k] = (gt[3], gt[4], gt[5], k, gt[0], gt[1], gt[2], 0.0, 2.0 * k)
+    for name, v in DRIFT.items():
+        poses[name][N_KF - 1] += np.float32(v)
+    lp = loop_params(search_num=3)
+    model = M.perform(P, poses, corners, surfs, STAMP, lp)
+    return P, poses, corners, surfs, lp, model
+
+
+def pose_err(p, gt):
+    p, gt = np.asarray(p, np.float64), np.asarray(gt, np.float64)
+    return float(np.linalg.norm(p[3:] - gt[3:])), float(abs(np.angle(np.exp(1j * (p[2] - gt[2])))))
+
+
+def test_model_closes_the_loop_on_the_fixture():
+    P, poses, corners, surfs, lp, m = fixture()
+    assert m["status"] == FBR_LOOP_CLOSED and (m["latest_id"], m["closest_id"]) == (19, 0)
+    assert m["n_target"] < m["n_raw"] and m["n_source"] == len(corners[19]) + len(surfs[19])
+    r = m["icp"]
+    assert r["converged"] == 1 and r["convergence"] == FBR_ICP_TRANSFORM and 3 <= r["iterations"] <= 30
+    assert r["fitness"] < 0.05
+    # a condition on the input: no convergence test of any iteration is decided within 10 % of its
+    # threshold, so float-rounding differences cannot change the iteration count
+    for tests in r["log"]:
+        for value, thr in tests:
+            assert not 0.9 * thr <= value <= 1.1 * thr, (value, thr)
+    gt = gt_pose(19)
+    dt, dyaw = pose_err(m["pose_corrected"], gt)
+    assert dt < 0.02 and dyaw < 5e-3, (dt, dyaw)
+    dt0, dyaw0 = pose_err(M.pose_of(poses[19]), gt)
+    assert dt < dt0 and dyaw < dyaw0
+
+
+def test_model_detect_takes_the_nearest_old_enough_keyframe():
+    _, poses, _, _, lp, _ = fixture()
+    assert M.detect(poses, STAMP, lp) == (19, 0)
+    assert M.detect(poses, STAMP, loop_params(search_time_diff=100.0)) is None
+    # seen from keyframe 18, keyframes 1 (0.4 m away) and 0 (1.6 m) are both old enough: the nearest
+    # hit wins, not the oldest
+    assert M.detect(poses[:19], 36.5, lp) == (18, 1)
+    assert M.detect(poses[:1], 0.5, lp) is None and M.detect(poses[:0], 0.5, lp) is None
+
+
+# ---- GPU: the correspondence search ---------------------------------------------------------------
+def cloud(xyz):
+    xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
+    c = np.zeros(len(xyz), POINT_XYZI)
+    c["x"], c["y"], c["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    return c
+
+
+def nn1_cases():
+    rng = np.random.default_rng(5)
+    cube = lambda n, lo=0.0, hi=10.0: rng.uniform(lo, hi, (n, 3)).astype(np.float32)
+    cases = {}
+    cases["one_target"] = (cube(1), cube(65), 100.0)
+    cases["one_query"] = (cube(300), cube(1), 100.0)
+    cases["q65"] = (cube(300), cube(65), 100.0)
+    cases["t1025"] = (cube(1025, 0.0, 4.0), cube(300, -1.0, 5.0), 100.0)  # dense: the grid finishes most
+    t = cube(200)
+    cases["duplicates"] = (np.concatenate([t, t[::-1], t]), np.concatenate([t[:40], cube(40)]), 100.0)
+    cases["query_on_target"] = (t, t[[3, 77, 199]], 100.0)
+    # two nearest targets at equal d2: exactly representable offsets on either side of the query
+    tt = np.array([[1.0, 1.0, 1.0], [5.0, 5.0, 5.0], [2.0, 1.0, 1.0], [1.5, 1.5, 1.0], [1.5, 0.5, 1.0]], np.float32)
+    cases["equal_d2"] = (tt, np.array([[1.5, 1.0, 1.0], [1.25, 1.0, 1.0]], np.float32), 100.0)
+    far = cube(300) + np.float32([90.0, 0.0, 0.0])  # 80 m outside the 10 m cube: the far kernel
+    cases["far"] = (cube(300), np.concatenate([far[:64], far[:6] * np.float32([-1, 1, 1])]), 200.0)
+    # three far-kernel workgroups of queries against three LDS tiles of targets
+    cases["far_tiles"] = (cube(2100), cube(600) + np.float32([0.0, -90.0, 3.0]), 200.0)
+    cases["gate_admits_equal"] = (np.array([[0.0, 0.0, 0.0], [9.0, 9.0, 9.0]], np.float32),
+                                  np.array([[2.0, 0.0, 0.0], [0.0, 2.0, 0.0], [2.5, 0.0, 0.0]], np.float32), 2.0)
+    cases["gate_excludes_all"] = (cube(300), cube(65) + np.float32(3.0), 1e-3)
+    q = cube(20)
+    q[3, 1] = np.nan
+    q[7] = np.nan
+    cases["nan_query"] = (cube(300), q, 100.0)
+    return cases
+
+
+@pytest.fixture(scope="module")
+def plain_ctx():
+    with api.Context(default_params(16, 1800)) as ctx:
+        yield ctx
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(nn1_cases()))
+def test_nn1_equals_brute_force(plain_ctx, name):
+    target, query, gate = nn1_cases()[name]
+    ref_i, ref_d = M.nn1(target, query, gate)
+    idx, d2 = plain_ctx.selftest_nn1(cloud(target), cloud(query), gate)
+    assert np.array_equal(idx, ref_i), (idx, ref_i)
+    assert np.array_equal(d2.view(np.uint32), ref_d.view(np.uint32))
+    if name == "gate_admits_equal":
+        assert list(idx) == [0, 0, -1] and d2[0] == 4.0
+    if name == "gate_excludes_all":
+        assert (idx == -1).all()
+    if name == "equal_d2":
+        assert list(idx) == [0, 0]  # (1,1,1) and (2,1,1) tie at 0.25 for the first: lowest index
+    if name == "duplicates":
+        assert (idx[:40] == np.arange(40)).all()  # the first of the three copies
+    if name == "query_on_target":
+        assert list(idx) == [3, 77, 199] and (d2 == 0).all()
+    if name == "nan_query":
+        assert idx[3] == -1 and idx[7] == -1 and (np.delete(idx, [3, 7]) >= 0).all()
+
+
+# ---- GPU: the loop call on the fixture -------------------------------------------------------------
+def add_keyframes(ctx, poses, corners, surfs, n=None):
+    for k in range(len(poses) if n is None else n):
+        ctx.keyframes_add(poses[k], corners[k], surfs[k])
+
+
+@pytest.fixture(scope="module")
+def loop_ctx():
+    P, poses, corners, surfs, _, _ = fixture()
+    with api.Context(P) as ctx:
+        add_keyframes(ctx, poses, corners, surfs)
+        yield ctx
+
+
+def raw_bytes(r):
+    return ctypes.string_at(ctypes.addressof(r), ctypes.sizeof(r))
+
+
+@pytest.mark.gpu
+def test_loop_closure_matches_model(loop_ctx):
+    P, poses, corners, surfs, lp, m = fixture()
+    ctx = loop_ctx
+    assert ctx.detect_loop_closure(STAMP, lp) == (19, 0)
+    r1 = ctx.perform_loop_closure(STAMP, lp, raw=True)
+    r2 = ctx.perform_loop_closure(STAMP, lp, raw=True)
+    assert raw_bytes(r1) == raw_bytes(r2)  # no arrival-order dependence
+    d = r1.as_dict()
+    mi = m["icp"]
+    print("device:", d["icp"]["iterations"], d["icp"]["convergence"], d["icp"]["fitness"], d["pose_corrected"])
+    print("model: ", mi["iterations"], mi["convergence"], mi["fitness"], m["pose_corrected"])
+    assert d["status"] == FBR_LOOP_CLOSED and (d["latest_id"], d["closest_id"]) == (19, 0)
+    assert (d["n_source"], d["n_target"]) == (m["n_source"], m["n_target"])
+    assert (d["icp"]["iterations"], d["icp"]["convergence"]) == (mi["iterations"], mi["convergence"])
+    assert d["icp"]["converged"] == 1
+    pc, pm = np.asarray(d["pose_corrected"], np.float64), np.asarray(m["pose_corrected"], np.float64)
+    dpos = np.abs(pc[3:] - pm[3:]).max()
+    drot = np.abs(np.angle(np.exp(1j * (pc[:3] - pm[:3])))).max()
+    print("device - model pose difference: %.3g m, %.3g rad" % (dpos, drot))
+    assert dpos <= POSE_TOL and drot <= POSE_TOL
+    assert np.array_equal(d["pose_closest"], M.pose_of(poses[0]))
+    T = d["icp"]["transform"].reshape(4, 4)
+    assert list(T[3]) == [0.0, 0.0, 0.0, 1.0]
+    fit = M.fitness(M.xyz(m["source"]), M.xyz(m["target"]), T)
+    assert abs(d["icp"]["fitness"] - fit) <= 1e-5 * fit, (d["icp"]["fitness"], fit)
+    btw = M.between(d["pose_corrected"], d["pose_closest"])
+    assert np.abs(d["between"].reshape(4, 4) - btw).max() <= 1e-5
+    gt = gt_pose(19)
+    dt, dyaw = pose_err(d["pose_corrected"], gt)
+    dt0, dyaw0 = pose_err(M.pose_of(poses[19]), gt)
+    assert dt < dt0 and dyaw < dyaw0, (dt, dt0, dyaw, dyaw0)
+    # the calls change no key pose
+    assert ctx.detect_loop_closure(STAMP, lp) == (19, 0) and ctx.keyframes_count() == N_KF
+
+
+@pytest.mark.gpu
+def test_loop_closure_leaves_the_registration_map_alone():
+    P, poses, corners, surfs, lp, m = fixture()
+    cmap, smap = synth.config_map("C1")
+    gt, guess = synth.job(3)
+    f = O.Stream(P).features(synth.scan(gt, 16, 1800, seed=3))
+    with api.Context(P) as ctx:
+        ctx.set_map(cmap, smap)
+        add_keyframes(ctx, poses, corners, surfs)
+        c0, s0 = ctx.get_map()
+        p0, st0 = ctx.register(f["corner"], f["surf"], guess)
+        assert ctx.perform_loop_closure(STAMP, lp)["status"] == FBR_LOOP_CLOSED
+        c1, s1 = ctx.get_map()
+        p1, st1 = ctx.register(f["corner"], f["surf"], guess)
+    assert c0.tobytes() == c1.tobytes() and s0.tobytes() == s1.tobytes()
+    assert p0.tobytes() == p1.tobytes() and st0 == st1
+
+
+@pytest.mark.gpu
+def test_loop_closure_status_paths(loop_ctx):
+    P, poses, corners, surfs, lp, m = fixture()
+    ctx = loop_ctx
+    r = ctx.perform_loop_closure(STAMP, loop_params(search_num=3, search_time_diff=100.0), raw=True)
+    assert (r.status, r.latest_id, r.closest_id) == (FBR_LOOP_NO_CANDIDATE, -1, -1)
+    zero = type(r)()
+    zero.status, zero.latest_id, zero.closest_id = FBR_LOOP_NO_CANDIDATE, -1, -1
+    assert raw_bytes(r) == raw_bytes(zero)  # the remaining fields are zero
+    assert ctx.detect_loop_closure(STAMP, loop_params(search_time_diff=100.0)) is None
+
+    r = ctx.perform_loop_closure(STAMP, loop_params(search_num=3, fitness_score=0.001))
+    assert r["status"] == FBR_LOOP_REJECTED_FITNESS
+    assert r["icp"]["converged"] == 1 and r["icp"]["iterations"] == m["icp"]["iterations"]
+    assert r["icp"]["fitness"] > 0.001 and (r["latest_id"], r["closest_id"]) == (19, 0)
+
+    r = ctx.perform_loop_closure(STAMP, loop_params(search_num=3, icp=dict(max_correspondence_distance=1e-4)))
+    assert r["status"] == FBR_LOOP_NOT_CONVERGED
+    assert (r["icp"]["converged"], r["icp"]["convergence"], r["icp"]["iterations"]) == (0, FBR_ICP_NO_CORRESPONDENCES, 0)
+    assert r["icp"]["n_correspondences"] < 3
+
+    r = ctx.perform_loop_closure(STAMP, loop_params(search_num=3, icp=dict(max_iterations=3)))
+    assert (r["icp"]["converged"], r["icp"]["convergence"], r["icp"]["iterations"]) == (1, FBR_ICP_ITERATIONS, 3)
+
+
+@pytest.mark.gpu
+def test_loop_closure_default_voxel_order(plain_ctx):
+    """The default VoxelGrid sums a voxel's points in index order, so the target's centroids differ
+    from the model's in the last bits: same candidate, sizes and iteration count, the pose within the
+    standing 1e-4."""
+    P, poses, corners, surfs, lp, m = fixture()
+    ctx = plain_ctx
+    ctx.keyframes_reset()
+    add_keyframes(ctx, poses, corners, surfs)
+    d = ctx.perform_loop_closure(STAMP, lp)
+    ctx.keyframes_reset()
+    assert d["status"] == FBR_LOOP_CLOSED and (d["latest_id"], d["closest_id"]) == (19, 0)
+    assert (d["n_source"], d["n_target"]) == (m["n_source"], m["n_target"])
+    assert (d["icp"]["iterations"], d["icp"]["convergence"]) == (m["icp"]["iterations"], m["icp"]["convergence"])
+    pc, pm = np.asarray(d["pose_corrected"], np.float64), np.asarray(m["pose_corrected"], np.float64)
+    assert np.abs(pc[3:] - pm[3:]).max() <= POSE_TOL
+    assert np.abs(np.angle(np.exp(1j * (pc[:3] - pm[:3])))).max() <= POSE_TOL
+    # target centroids move by at most the keyframe maps' 2e-4 m bar (tests/test_keyframes.py), so a
+    # mean squared distance of rms d changes by at most 2 d 2e-4
+    fm = m["icp"]["fitness"]
+    assert abs(d["icp"]["fitness"] - fm) <= 2.0 * np.sqrt(fm) * 2e-4
+
+
+@pytest.mark.gpu
+def test_loop_closure_without_history(plain_ctx):
+    P, poses, corners, surfs, lp, _ = fixture()
+    ctx = plain_ctx
+    ctx.keyframes_reset()
+    assert ctx.perform_loop_closure(0.5, lp)["status"] == FBR_LOOP_NO_CANDIDATE  # no keyframe: not an error
+    assert ctx.detect_loop_closure(0.5, lp) is None
+    add_keyframes(ctx, poses, corners, surfs, n=1)
+    r = ctx.perform_loop_closure(100.0, lp)  # the only hit is the last keyframe itself
+    assert (r["status"], r["latest_id"], r["closest_id"]) == (FBR_LOOP_NO_CANDIDATE, -1, -1)
+    ctx.keyframes_reset()
+
+
+# ---- GPU: fbr_icp_align ----------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_icp_align_equals_the_loop_call(loop_ctx):
+    P, poses, corners, surfs, lp, m = fixture()
+    loop = loop_ctx.perform_loop_closure(STAMP, lp, raw=True)
+    r = loop_ctx.icp_align(m["source"], m["target"], icp_params(), raw=True)
+    assert raw_bytes(r) == raw_bytes(loop.icp)
+
+
+@pytest.mark.gpu
+def test_icp_align_needs_three_correspondences(plain_ctx):
+    rng = np.random.default_rng(9)
+    src = cloud(rng.uniform(0, 5, (2, 3)))
+    tgt = cloud(rng.uniform(0, 5, (10, 3)))
+    r = plain_ctx.icp_align(src, tgt)
+    assert (r["converged"], r["convergence"], r["iterations"], r["n_correspondences"]) == (
+        0, FBR_ICP_NO_CORRESPONDENCES, 0, 2)
+    assert np.array_equal(r["transform"].reshape(4, 4), np.eye(4, dtype=np.float32))
+    assert abs(r["fitness"] - M.fitness(M.xyz(src), M.xyz(tgt), np.eye(4, dtype=np.float32))) <= 1e-12
