@@ -3238,6 +3238,10 @@ int icp_prepare(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt
     while (cell < hint && cell < 64.0f) cell *= 2.0f;
     for (int tries = 0; tries < 8; ++tries, cell *= 2.0f) {
       rc = grid_build_device(c->stream, c->arena, d_tgt, nt, 1.0f / cell, 1.0f / cell, false, c->icp_grid);
+      if (rc == FBR_ERR_CAPACITY) {  // (nt is in range: the box has too many cells even for chunks)
+        rc = FBR_OK;
+        continue;
+      }
       if (rc) return rc;
       const GridDesc& g = c->icp_grid.g;
       if (!g.sparse && (int64_t)g.n_cells <= std::max<int64_t>((int64_t)1 << 22, 64 * nt)) {

@@ -331,8 +331,10 @@ int fbr_extract_surrounding_keyframes(fbr_ctx* ctx, double stamp, const fbr_keyf
  *          (the square taken in double); non-finite points have none
  *     fewer than 3 correspondences: converged = 0, FBR_ICP_NO_CORRESPONDENCES, stop
  *     T = Umeyama without scaling over the correspondences in double (means, sigma = sum (t - mt)
- *         (s - ms)^T / n, SVD, S = diag(1, 1, det(sigma) < 0 ? -1 : 1), R = U S V^T,
- *         t = mt - R ms), rounded to float
+ *         (s - ms)^T / n, SVD sigma = U diag(w) V^T, S = diag(1, 1, det(U) det(V) < 0 ? -1 : 1),
+ *         R = U S V^T, t = mt - R ms), rounded to float.  R is always a proper rotation
+ *         (det R = +1), for planar and collinear correspondences too, where the sign of
+ *         det(sigma) would be rounding noise; for full-rank sigma the two signs agree
  *     X[i] = T X[i] in float, rows ((r0 x + r1 y) + r2 z) + t; final = T final in float; ++it
  *     it >= max_iterations: converged = 1, FBR_ICP_ITERATIONS, stop
  *     cos = 0.5 (T00 + T11 + T22 - 1), t2 = |t|^2 in double; cos >= 1 - transformation_epsilon and

@@ -74,12 +74,13 @@ def compose(A, B):
 
 
 def umeyama(s, t):
-    """Umeyama without scaling, float64: the 4x4 T with t ~ R s + tr, rounded to float32."""
+    """Umeyama without scaling, float64: the 4x4 T with t ~ R s + tr, rounded to float32.  The sign
+    comes from det(U) det(V), not det(sigma), so R is a proper rotation for a planar cloud too."""
     s, t = np.asarray(s, np.float64), np.asarray(t, np.float64)
     ms, mt = s.mean(0), t.mean(0)
     sigma = (t - mt).T @ (s - ms) / len(s)
     U, _, Vt = np.linalg.svd(sigma)
-    S = np.diag([1.0, 1.0, -1.0 if np.linalg.det(sigma) < 0 else 1.0])
+    S = np.diag([1.0, 1.0, -1.0 if np.linalg.det(U) * np.linalg.det(Vt) < 0 else 1.0])
     R = U @ S @ Vt
     T = np.eye(4)
     T[:3, :3] = R

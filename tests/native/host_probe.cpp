@@ -1,6 +1,7 @@
 // Host-compiled probes of the device headers (test infrastructure): the same source the kernels
-// use (fbr_fdlibm.h, fbr_sort.h), compiled for the CPU so the tests can compare it with the
-// reference's real dependencies (glibc atan2f, libstdc++ std::sort) without a GPU.
+// use (fbr_fdlibm.h, fbr_sort.h, fbr_icp_solve.h), compiled for the CPU so the tests can compare it
+// with the reference's real dependencies (glibc atan2f, libstdc++ std::sort) or a float64 model
+// without a GPU.
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "fbr_fdlibm.h"
+#include "fbr_icp_solve.h"
 #include "fbr_sincosf.h"
 #include "fbr_sort.h"
 
@@ -59,6 +61,12 @@ void probe_sort(const float* values, int64_t n, int64_t* ind_out) {
   fbr::std_sort_emul(a, (int)n);
   for (int64_t i = 0; i < n; ++i) ind_out[i] = a[i].ind;
   delete[] a;
+}
+
+// k_icp_solve's transformation estimate (fbr_icp_solve.h) on n sets of the 17 correspondence sums:
+// the row-major 3x4 float T of each.
+void probe_icp_umeyama(const double* sums, float* T, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) fbr::icp_umeyama(sums + 17 * i, T + 12 * i);
 }
 
 }

@@ -150,6 +150,66 @@ def nn1_cases():
     q[3, 1] = np.nan
     q[7] = np.nan
     cases["nan_query"] = (cube(300), q, 100.0)
+
+    # k_icp_far's tile loop a second time round (more than 32 x 1024 targets), and a nearest point that
+    # exists twice: in tiles of different y-splits (the atomicMin decides) and in two tiles of the same
+    # split (the thread's own running best decides).  Either way the lowest index wins.
+    t = cube(32 * 1024 + 1025)
+    t[5000] = t[33000] = (10.5, 5.0, 5.0)    # tiles 4 and 32: y-splits 4 and 0
+    t[100] = t[32768 + 100] = (10.5, 2.0, 8.0)  # tiles 0 and 32: both y-split 0
+    q = cube(70) + np.float32([90.0, 0.0, 0.0])
+    q[0], q[1] = (95.0, 5.0, 5.0), (95.0, 2.0, 8.0)
+    cases["far_stride"] = (t, q, 200.0)
+    # one target so far out that the box has more than kDenseGridCells cells at every one of the eight
+    # cell sizes (0.5 m .. 64 m): no grid, every query goes to the far kernel
+    cluster = cube(300)
+    cases["no_grid"] = (np.concatenate([cluster, np.float32([[1e5, 1e5, 1e5]])]),
+                        np.concatenate([cube(60), cube(5) + np.float32(1e5), cube(5) + np.float32(5e4)]), 1e6)
+    # the grid is accepted only at 16 m cells; queries inside the cluster, at the outlier and between
+    cases["doubled_cell"] = (np.concatenate([cluster, np.float32([[3000.0, 3000.0, 300.0]])]),
+                             np.concatenate([cube(60), cube(10, -40.0, 50.0),
+                                             cube(5) + np.float32([3000.0, 3000.0, 300.0]),
+                                             cube(5) + np.float32([1500.0, 1500.0, 150.0])]), 1e4)
+    # the shell limit: 0.5 m cells over a 2 m cube (cells -2 .. 1 on every axis); queries in the cells 3
+    # outside it (searched on the grid) and 4 outside it (queued), on both sides of every axis, at the
+    # cells' first float, last float and middle
+    t = cube(400, -1.0, 1.0)
+    below = lambda v: np.nextafter(np.float32(v), np.float32(-np.inf))
+    edges = [-2.5, below(-2.0), -2.25, -3.0, below(-2.5), -2.75,  # cells -5 and -6
+             2.0, below(2.5), 2.25, 2.5, below(3.0), 2.75]        # cells 4 and 5
+    q = []
+    for axis in range(3):
+        for e in edges:
+            for _ in range(3):
+                p = rng.uniform(-1.0, 1.0, 3)
+                p[axis] = e
+                q.append(p)
+    q += [[e, e, e] for e in edges] + [[edges[k], edges[(k + 6) % 12], edges[k]] for k in range(12)]
+    cases["shell_edge"] = (t, np.float32(q), 1000.0)
+    # targets and queries on exact multiples of the 0.5 m cell and on the float just below them: cell
+    # assignment at the edges, and many equal distances
+    g = np.float32([-1.0, -0.5, 0.0, 0.5, 1.0])
+    g = np.concatenate([g, below(g)])
+    lat = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    cases["cell_edges"] = (lat[rng.permutation(len(lat))],
+                           np.concatenate([lat[rng.permutation(len(lat))[:200]], lat[:60] + np.float32(0.25),
+                                           cube(40, -1.5, 1.5)]), 100.0)
+    # NaN and Inf target points are no candidates, and the indices returned are the original ones
+    t = cube(300)
+    t[[0, 17, 150, 299]] = np.nan
+    t[[5, 200], 2] = np.inf
+    t[[60, 61]] = -np.inf
+    t[250, 0] = np.nan
+    cases["nan_target"] = (t, np.concatenate([cube(60), t[[1, 16, 18, 298]], far[:20]]), 200.0)
+    q = cube(20)
+    q[2], q[9, 0], q[11, 2], q[19] = np.inf, np.inf, -np.inf, (np.inf, np.nan, 1.0)
+    cases["inf_query"] = (cube(300), q, 100.0)
+    # cell indices beyond 1e7 (not exact in float) and just below; some inside the gate, some not
+    q = np.float32([[6e6, 5.0, 5.0], [-6e6, 5.0, 5.0], [5.0, 6e6, 5.0], [5.0, 5.0, -6e6], [6e6, 6e6, 6e6],
+                    [-6e6, 6e6, -6e6], [4e6, 5.0, 5.0], [5.0, -4e6, 4e6], [6e6, -6e6, 5.0]])
+    cases["huge_query"] = (cube(300), np.concatenate([q, cube(5)]), 1e7)
+    cases["empty_target"] = (np.zeros((0, 3), np.float32), cube(65), 100.0)
+    cases["no_query"] = (cube(300), np.zeros((0, 3), np.float32), 100.0)
     return cases
 
 
@@ -179,6 +239,24 @@ def test_nn1_equals_brute_force(plain_ctx, name):
         assert list(idx) == [3, 77, 199] and (d2 == 0).all()
     if name == "nan_query":
         assert idx[3] == -1 and idx[7] == -1 and (np.delete(idx, [3, 7]) >= 0).all()
+    if name == "far_stride":
+        assert list(idx[:2]) == [5000, 100] and (idx >= 0).all()
+    if name == "shell_edge":
+        lo, hi = np.floor(target.min(0) * 2), np.floor(target.max(0) * 2)
+        out = np.maximum(lo - np.floor(query * 2), np.floor(query * 2) - hi).max(1)
+        assert (lo == -2).all() and (hi == 1).all() and set(out) == {3.0, 4.0} and (idx >= 0).all()
+    if name == "nan_target":
+        assert (idx >= 0).all() and np.isfinite(target[idx]).all() and list(idx[60:64]) == [1, 16, 18, 298]
+    if name == "inf_query":
+        assert [i for i in range(20) if idx[i] < 0] == [2, 9, 11, 19]
+    if name == "huge_query":
+        assert [i for i in range(len(idx)) if idx[i] < 0] == [4, 5]
+    if name == "empty_target":
+        assert len(idx) == 65 and (idx == -1).all() and (d2 == np.finfo(np.float32).max).all()
+    if name == "no_query":
+        assert len(idx) == 0 and len(d2) == 0
+    if name in ("no_grid", "doubled_cell"):
+        assert (idx >= 0).all() and (idx == len(target) - 1).any() and (idx < len(target) - 1).any()
 
 
 # ---- GPU: the loop call on the fixture -------------------------------------------------------------
