@@ -1,0 +1,434 @@
+// fbr_ctx.h — internal to the host units (fbr_*.hip): the context behind include/fbr.h's opaque
+// fbr_ctx, the small helpers every unit uses, and the few functions that cross units.
+//
+//   fbr_api.hip     life cycle (the one allocation list and its frees), profiling timers, diagnostics
+//   fbr_stages.hip  per-stage launch glue, the Gauss-Newton run driver and its flag waits, results
+//   fbr_scan.hip    single-scan entry points, their upload path and copy-worker pool
+//   fbr_batch.hip   batch stage / launch / export state machine, the pinned-ring ingest
+//   fbr_comm.hip    RCCL communicator and pose gather
+//   fbr_map.hip     map VoxelGrid and kNN grids, keyframe store and local map, pose helpers
+//   fbr_loop.hip    loop closure candidate search and ICP
+//
+// Everything shared lives in fbr::internal, which is hidden: the library's link exports every
+// default-visibility symbol, and none of this is part of its interface.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <set>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "fbr_common.h"
+#include "fbr_imu.h"
+#include "fbr_kernels.h"
+#include "fbr_knobs.h"
+#include "fbr_msg.h"
+
+using namespace fbr;
+
+#define CK(x)                                                                        \
+  do {                                                                               \
+    hipError_t e_ = (x);                                                             \
+    if (e_ != hipSuccess) {                                                          \
+      fprintf(stderr, "fbr: HIP error %s at %s:%d\n", hipGetErrorString(e_), __FILE__, __LINE__); \
+      return FBR_ERR_HIP;                                                            \
+    }                                                                                \
+  } while (0)
+
+namespace fbr {
+namespace internal __attribute__((visibility("hidden"))) {
+
+// Host wall time since t0 into DebugCounters::host_ns[k] (fbr_diag_host_times).
+inline void host_time(int k, std::chrono::steady_clock::time_point t0) {
+  const auto ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  debug_counters().host_ns[k].fetch_add((long long)ns, std::memory_order_relaxed);
+}
+
+// Blocking host synchronisations, counted (fbr_debug_counters).
+inline hipError_t fbr_sync(hipStream_t s) {
+  debug_counters().host_syncs.fetch_add(1, std::memory_order_relaxed);
+  return hipStreamSynchronize(s);
+}
+inline hipError_t fbr_memcpy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+  debug_counters().host_syncs.fetch_add(1, std::memory_order_relaxed);
+  return hipMemcpy(dst, src, bytes, kind);
+}
+
+template <typename T>
+int dalloc(T** p, size_t count) {
+  *p = nullptr;
+  if (count == 0) count = 1;
+  CK(hipMalloc((void**)p, sizeof(T) * count));
+  return FBR_OK;
+}
+
+// Grow a device array to hold `need` elements (keeping `keep` of them).
+template <typename T>
+int grow(T** p, int64_t* cap, int64_t need, int64_t keep, hipStream_t st) {
+  if (need <= *cap) return FBR_OK;
+  const int64_t ncap = std::max<int64_t>(need, *cap * 2 + 1024);
+  T* q = nullptr;
+  CK(hipMalloc((void**)&q, sizeof(T) * ncap));
+  if (*p && keep > 0) CK(hipMemcpyAsync(q, *p, sizeof(T) * keep, hipMemcpyDeviceToDevice, st));
+  CK(fbr_sync(st));
+  if (*p) CK(hipFree(*p));
+  *p = q;
+  *cap = ncap;
+  return FBR_OK;
+}
+
+struct KernelTimer {
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+  double total_ms = 0.0;
+  int64_t launches = 0;
+};
+
+}  // namespace internal
+}  // namespace fbr
+using namespace fbr::internal;
+
+constexpr int kMaxSub = 8;  // sub-batch streams per launch (FBR_NSUB); more than 3 pays only with
+                             // GPU_MAX_HW_QUEUES above HIP's default of 4 (one hardware queue per stream)
+
+// Host ingest of fbr_process_batch: the caller's (pageable) scans are packed into a ring of pinned
+// staging chunks by host threads and copied to HBM on a copy stream, into the input slot the
+// running device batch does not read; batch k+1's upload overlaps batch k's compute.
+struct Ingest {
+  static constexpr int kChunks = 4;
+  hipStream_t cstream = nullptr;
+  hipStream_t xstream = nullptr;     // k_expand_scans, off the copy stream (FBR_INGEST_XSTREAM=0: on it)
+  hipEvent_t copied_ev = nullptr;    // the copies of the current upload are done (on cstream)
+  hipEvent_t up_ev[2] = {};          // the upload of input slot s is complete (on xstream / cstream)
+  hipEvent_t chunk_ev[kChunks] = {};  // the copies out of chunk k are complete
+  bool chunk_used[kChunks] = {};
+  int next_chunk = 0;
+  uint8_t* h_stage = nullptr;        // kChunks x chunk_bytes, pinned
+  int64_t chunk_bytes = 0;
+  fbr_point_xyzirt* d_pts_slot[2] = {};  // slot 0 = the context's scan buffer, slot 1 allocated here
+  int nthreads = 8;                  // packing threads per chunk
+  double h2d_bytes = 0.0;            // bytes copied host -> device by the last fbr_process_batch
+  // Compact records (no deskew tables set: `time` is never read): per scan the x, y, z planes
+  // (f32) and the rings (u8 below 256 rings), 13 B per point instead of 24, expanded on the device
+  // by k_expand_scans (the batch returns poses and statistics, which no point's intensity or time
+  // reaches).
+  uint8_t* d_stage[2] = {};          // per input slot: [Bcap][ingest_region_bytes(NMAX)] (one per
+                                     // slot, so slot s's expand overlaps slot s^1's copies)
+  int64_t* d_nin = nullptr;          // [2][2][Bcap] per input slot: the staged scans' point counts,
+                                     // then their records' byte offsets in d_stage (copy stream)
+  int64_t* h_nin = nullptr;          // [2][2][Bcap] pinned
+  bool compact_used = false;         // the last fbr_process_batch used compact records
+  bool pk_slot[2] = {};              // input slot s holds 16-B device records (launch_expand_scans pk)
+};
+
+// A contiguous sub-batch of jobs driven on one stream.  j0 is the first job of the sub-batch's
+// work buffers (every per-job intermediate array, and the Gauss-Newton work-item arrays at
+// j0 * items_per_job); in0 the first job of its inputs (raw scans, counts, guesses, deskew tables,
+// CropBox statistics).  A batch launch in work slot s has j0 = s * max_batch + in0, so two launches
+// in flight never share intermediates.  k indexes the sub-batch's GN flags / counters.
+struct Sub {
+  int j0, B, k;  // first work job, job count, GN flag index (< kMaxSub)
+  hipStream_t st;
+  bool stream_mode = false;  // single-scan call (carries stream state) vs independent batch jobs
+  int in0 = 0;               // first input job
+};
+
+// The Gauss-Newton iterations of one launch that the host has still to enqueue.  The host stays
+// `lag` (gn_lag) iterations ahead of each sub-batch and stops once its k_gn_solve reports that no job is
+// active (flags in host-mapped memory), so a launch's tail cannot be enqueued before the device
+// has run most of it; two launches in flight are advanced together (fbr_batch_launch).
+struct GnRun {
+  bool pending = false;
+  bool trace = false;
+  int nsub = 0;
+  unsigned long long gen = 0;
+  Sub subs[kMaxSub];
+  GnArgs a[kMaxSub];
+  bool live[kMaxSub] = {}, watch[kMaxSub] = {}, done[kMaxSub] = {};
+  int lag = 2;               // gn_lag: iterations enqueued ahead of the latest flag read
+  int active[kMaxSub] = {};  // jobs still iterating `lag` iterations ago (an upper bound now)
+  int it[kMaxSub] = {};      // next iteration to enqueue
+  long polls[kMaxSub] = {};  // unanswered flag reads of the current wait
+  std::chrono::steady_clock::time_point wait0[kMaxSub];  // start of the current wait
+  int64_t next_query[kMaxSub] = {};  // ns into the current wait of the next stream query
+};
+
+// A flag wait asks the runtime whether the stream drained (flags not visible although the work
+// is done) only once it has lasted several times longer than the waits of its kind usually do:
+// hipStreamQuery puts a marker into the stream, and a marker between two iterations' kernels cost
+// ~5.7 us on the device (every launch enqueued after a wait had one).  The bound is 4x the
+// smoothed duration of the completed waits of that kind (GN flags of batch runs, of single-scan
+// runs, single-scan direct results), within [kQueryMinNs, kQueryMaxNs]; queries repeat at most
+// every half bound.  (Round 5 used a fixed 2 ms, which a late-visible flag turned into a 2 ms scan.)
+// The floor stays above the longest normal single-scan wait (0.44 ms measured, r06c): at 150 us
+// about one wait per scan queried its stream, and each query is a marker before the next kernel.
+constexpr int64_t kQueryMinNs = 500000, kQueryMaxNs = 2000000;
+struct WaitBound {
+  double ema_ns = 0.0;
+  int64_t after() const {
+    return ema_ns <= 0.0 ? kQueryMaxNs : std::min<int64_t>(kQueryMaxNs, std::max<int64_t>(kQueryMinNs, (int64_t)(4.0 * ema_ns)));
+  }
+  void done(int64_t ns) { ema_ns = ema_ns <= 0.0 ? (double)ns : 0.875 * ema_ns + 0.125 * (double)ns; }
+};
+enum { kWaitBatchFlag = 0, kWaitScanFlag = 1, kWaitDirect = 2 };
+
+// Members stand under the unit that owns them: the unit that gives them their meaning and, but for
+// the allocation list, writes them.  fbr_create / fbr_destroy (fbr_api.hip) allocate and free every
+// array that is not "grown on demand" or "allocated on first use".
+struct fbr_ctx {
+  fbr_params P;
+  int dev = 0;
+  int H = 0, W = 0, Bcap = 0;
+  int64_t HW = 0, NMAX = 0;
+  int items_per_job = 0;
+  int max_items = 0;
+
+  // ---- streams and events (fbr_api.hip creates them; every unit enqueues on them) ----
+  hipStream_t stream = nullptr;   // primary stream (single-scan calls, batch sub-batch 0, export)
+  hipStream_t xstream[kMaxSub] = {};  // extra streams of batch sub-batches 1.. (index 0 unused)
+  hipEvent_t xev[kMaxSub] = {};       // fork / join events
+  hipEvent_t ev_staged = nullptr;  // the staged inputs are on the device (recorded on stream)
+  hipEvent_t ev_fork = nullptr;    // single-scan side-stream fork
+  hipEvent_t ev_ext = nullptr;     // a caller's stream, waited on before an export (fbr_batch_export_ready)
+  DevArena arena;                      // scratch of the set-up paths (map VoxelGrid, grid builds)
+
+  // ---- stage inputs and work arrays: projection, features, mapping DS (fbr_stages.hip) ----
+  // inputs
+  fbr_point_xyzirt* d_pts = nullptr;
+  int64_t* d_nin = nullptr;
+  float* d_guess = nullptr;
+  // projection
+  // owner image generations (OwnerTag, fbr_kernels.h): owner_ib index bits, owner_tmax the last
+  // generation before the image is refilled (0: untagged, reset by k_compact)
+  int owner_ib = 0;
+  uint32_t owner_gen = 0, owner_tmax = 0;
+  int32_t *d_owner = nullptr, *d_rowcnt = nullptr, *d_col = nullptr, *d_start = nullptr, *d_end = nullptr,
+          *d_nvalid = nullptr;
+  float4* d_cloud = nullptr;
+  float* d_range = nullptr;
+  // features
+  StreamState* d_sstate = nullptr;    // [Bcap] batch (zeroed per batch)
+  StreamState* d_sstream = nullptr;   // [1]   stream mode (persistent)
+  int8_t* d_label = nullptr;          // [Bcap][HW]
+  int8_t* d_label_stream = nullptr;   // [HW]   stream mode (persistent)
+  float4* d_corner_slot = nullptr;
+  int32_t* d_corner_cnt = nullptr;
+  float4* d_surf_ring = nullptr;
+  int32_t* d_surf_ring_cnt = nullptr;
+  float* d_ring_box = nullptr;  // [B][H][kRingBox]: k_concat's per-ring cloud bounds
+  bool ring_box_valid = false;  // d_corner_all / d_surf_all came from k_concat (not upload_cloud)
+  int32_t* d_err = nullptr;
+  float4 *d_corner_all = nullptr, *d_surf_all = nullptr, *d_cornerDS = nullptr, *d_surfDS = nullptr;
+  int32_t *d_ncorner = nullptr, *d_nsurf = nullptr, *d_ncds = nullptr, *d_nsds = nullptr;
+  uint32_t* d_vg_scratch = nullptr;
+  int64_t vg_scratch_elems = 0;
+  unsigned char* d_feat_scratch = nullptr;  // k_features sorted-path slots [B*H][gslot_bytes]
+  // IMU deskew (fbr_set_deskew, fbr_batch.hip, fills the tables)
+  fbr_deskew_table* d_desk = nullptr;  // [Bcap] tables (allocated on first use)
+  int32_t* d_desk_mode = nullptr;      // [Bcap] kDesk* bits per job
+  int32_t* d_rowmin = nullptr;         // [Bcap][H] minimum owner per row
+  int32_t* d_choff = nullptr;          // [Bcap][H][W / 32 + 1] compaction tile offsets
+  bool desk_any = false;               // some job has a non-zero mode
+  bool no_time_call = false;           // the current call's PointCloud2 has no "time" field
+
+  // ---- Gauss-Newton work arrays, run driver state and results (fbr_stages.hip) ----
+  GnState* d_gn = nullptr;
+  int4* d_items = nullptr;
+  int32_t *d_nitems = nullptr, *d_item_range = nullptr, *d_cropcnt = nullptr;
+  int32_t* d_cropwork = nullptr;  // [Bwork][2]: a launch's CropBox counts while they accumulate
+  double* d_partial = nullptr;
+  int32_t* d_nbr = nullptr;
+  float* d_fitc = nullptr;     // [max_items][6][256] per-query fit cache (k_gn_residual)
+  int8_t* d_fits = nullptr;    // [max_items][256]
+  int8_t* d_nsame = nullptr;   // [max_items][256]
+  // block-tile kNN (k_knn_tile.hip), allocated by build_map_grids when the map's grids take it:
+  int32_t* d_fb_list = nullptr;  // [3][max_items][256] queued / binned query slots, query blocks
+  int32_t* d_bin = nullptr;      // [kMaxSub][3][bin_nb] per-block counts, cursors, non-empty list
+  int64_t bin_nb = 0, bin_nb_c = 0;
+  unsigned long long* h_iter_flags = nullptr;  // host-mapped, written by k_gn_solve
+  unsigned long long* d_iter_flags = nullptr;  // its device address
+  unsigned long long gn_gen = 0;
+  int32_t* d_iter_cnt = nullptr;
+  WaitBound wait_bound[3];            // kWaitBatchFlag / kWaitScanFlag / kWaitDirect
+  int gn_items_hint = 0, gn_items_hint_B = 0;  // the last batch run's work items and its job count
+  // Work items of the previous single scan: the next one's Gauss-Newton grids are sized from it
+  // (2x, at least 16 workgroups) instead of from the capacity bound.  The kernels loop over the
+  // items whatever the grid, so the hint only moves time: the C2 bound of ~900 items launched
+  // ~870 workgroups (x 8 in the wide kNN mode) that found no item.
+  int items_hint = 0;
+  bool crop_cached = false;  // d_cropcnt holds the staged batch's CropBox statistics
+  float* d_pose_out = nullptr;
+  fbr_reg_stats* d_stats = nullptr;
+  float* d_trace = nullptr;
+  JobResult* d_result = nullptr;          // [Bcap] packed per-job results
+  JobResult* h_result = nullptr;          // [Bcap] pinned
+  std::vector<int32_t> last_iters, last_q, last_n, last_m;
+
+  // ---- single-scan state (fbr_scan.hip) ----
+  int64_t single_n = -1;  // the single-scan path's point count (k_project's argument, no copy)
+  bool have_projection = false;
+  double time_last = -1.0;
+  int stream_degenerate = 0;  // mapOptimization::isDegenerate across single-scan registrations
+  bool crop_join = false;    // single scan: copy_results takes the CropBox counts from h_crop (side stream)
+  int32_t* h_crop = nullptr;  // pinned [2]: the single-scan CropBox counts
+  float* h_guess = nullptr;   // pinned [6]: the single-scan guess (queue_guess)
+  fbr_point_xyzirt* h_scan = nullptr;     // [NMAX] pinned staging of single-scan uploads
+  int64_t* h_nin = nullptr;               // pinned scalar
+  uint8_t* d_msg = nullptr;                 // raw PointCloud2 bytes of the last *_msg call (grown on demand)
+  uint64_t msg_cap = 0;
+  uint8_t* h_msg = nullptr;               // pinned staging of raw PointCloud2 bytes (grown on demand)
+  uint64_t h_msg_cap = 0;
+  // fbr_process_scan's direct result (GnArgs::direct): the ending k_gn_solve packs the job's
+  // result into h_direct (host-mapped); the host spins on its generation word instead of
+  // enqueueing finalize + pack + copy and synchronising.  The no-op iterations the host had
+  // enqueued ahead of the last flag may still be queued when the call returns (tail_pending):
+  // the next single-scan call is ordered after them on the stream, every other entry point
+  // synchronises the stream first (enter).
+  JobResult* h_direct = nullptr;
+  JobResult* d_direct = nullptr;
+  int32_t* d_direct_done = nullptr;
+  int32_t direct_gen = 0;     // generation of the current single-scan run (0: direct off)
+  int32_t direct_gen_seq = 0;
+  bool tail_pending = false;
+
+  // ---- batch staging and launch slots (fbr_batch.hip) ----
+  int nsub_pref = 3;                  // sub-batches per batch launch (FBR_NSUB overrides): 3 unpipelined (at
+                                      // B = 128: 2 -> 76.1k, 3 -> 78.5k, 4 -> 46.7k scans/s), 1 pipelined
+  // Batch launches rotate over nslot work slots (fbr_params.pipeline_depth, default 3; 1 when max_batch = 1): the
+  // next launch's projection / features overlap the previous ones' Gauss-Newton tails.  Work arrays
+  // hold Bwork = nslot * Bcap jobs; inputs hold Bcap.
+  static constexpr int kMaxSlots = 3;
+  int nslot = 1;
+  int64_t Bwork = 0;
+  GnRun run[kMaxSlots];
+  int64_t launch_seq = 0;     // batch launches so far
+  int last_slot = -1;         // slot of the latest launch (-1: none since the last stage)
+  int64_t slot_launch[kMaxSlots] = {-1, -1, -1};  // launch number of each slot's latest launch
+  bool batch_full_masks = false;            // fbr_batch_set_full_masks: launches compute whole masks
+  bool slot_full_masks[kMaxSlots] = {};     // ... and which slots' latest launch did
+  int64_t exported = -1;      // latest launch whose records fbr_batch_export_ready exported
+  int64_t first_valid = 0;    // launches below this id belong to a dropped batch (fbr_batch_allgather)
+  int staged_B = 0;
+  std::vector<int64_t> staged_nin;
+  // the staged batch's 16-B device records (fbr_kernels.h: x, y, z, ring bits), null = the 24-B
+  // scans in d_pts; d_pk backs them for fbr_batch_stage (fbr_process_batch expands into its slots)
+  float4* d_pk = nullptr;
+  const float4* staged_pk = nullptr;
+  bool staged_24 = false;  // d_pts holds the staged batch's 24-B scans (a deskewing launch needs them)
+
+  // ---- ingest of fbr_process_batch (fbr_batch.hip) ----
+  Ingest ing;                 // fbr_process_batch host ingest (allocated on first use)
+
+  // ---- map grids (fbr_map.hip) ----
+  bool has_map = false;
+  DevGrid grid_c, grid_s;  // kNN grids of the corner / surf maps (k_grid.hip)
+  std::vector<fbr_point_xyzi> map_c_host, map_s_host;
+  bool map_nocrop = false;  // the registration map is a keyframe local map
+
+  // ---- keyframes (fbr_map.hip) ----
+  // LIO-SAM keyframe store (fbr_keyframes_*) and the local map built from it
+  std::vector<fbr_keypose> kf_poses;
+  std::vector<int64_t> kf_c_off, kf_c_cnt, kf_s_off, kf_s_cnt;
+  float4 *d_kf_c = nullptr, *d_kf_s = nullptr;  // lidar-frame keyframe clouds, appended
+  int64_t kf_c_cap = 0, kf_s_cap = 0, kf_c_used = 0, kf_s_used = 0;
+  float4 *d_kraw_c = nullptr, *d_kraw_s = nullptr;  // concatenated transformed clouds
+  int64_t kraw_c_cap = 0, kraw_s_cap = 0;
+  float4 *d_kds_c = nullptr, *d_kds_s = nullptr;    // their VoxelGrids (laserCloud*FromMapDS)
+  int64_t kds_c_n = 0, kds_s_n = 0;
+  KfSeg* d_kf_segs = nullptr;
+  int64_t kf_segs_cap = 0;
+  int* d_bounds = nullptr;
+
+  // ---- loop closure / ICP scratch (fbr_loop.hip) ----
+  // loop closure ICP (fbr_perform_loop_closure, fbr_icp_align): scratch of its own, grown on demand
+  float4 *d_icp_src = nullptr, *d_icp_x = nullptr, *d_icp_raw = nullptr, *d_icp_tgt = nullptr;
+  int64_t icp_src_cap = 0, icp_x_cap = 0, icp_raw_cap = 0, icp_tgt_cap = 0;
+  unsigned long long* d_icp_key = nullptr;
+  int32_t* d_icp_far = nullptr;       // [n + 1]: the far-query list, then its count
+  double* d_icp_partial = nullptr;
+  int64_t icp_key_cap = 0, icp_far_cap = 0, icp_partial_cap = 0;
+  KfSeg* d_icp_segs = nullptr;
+  int64_t icp_segs_cap = 0;
+  IcpState* d_icp_state = nullptr;    // the state, then the fbr_icp_result record
+  unsigned long long* h_icp_flag = nullptr;  // host-mapped stop word, written by k_icp_solve
+  unsigned long long* d_icp_flag = nullptr;
+  unsigned long long icp_gen = 0;
+  DevGrid icp_grid;                   // the ICP's own grid over its target
+
+  // ---- profiling (fbr_api.hip) ----
+  bool profiling = false;
+  std::map<std::string, KernelTimer> timers;
+  std::set<std::string> profile_only;  // empty: time every kernel
+
+  // ---- diagnostics (fbr_api.hip) ----
+  int diag_err_job = -1;      // diagnostic (fbr_diag_force_capacity_error): batch job flagged over capacity
+  int diag_ring_filter = -1;  // diagnostic (fbr_diag_ring_filter): per-ring surf filter kernel, -1 = by size
+  unsigned long long* d_feat_stamps = nullptr;  // diagnostic builds (FBR_FEAT_STAMPS) only
+  uint32_t* d_feat_paths = nullptr;             // tests (fbr_diag_feature_paths): FeatArgs::paths [Bwork][H]
+};
+
+namespace fbr {
+namespace internal __attribute__((visibility("hidden"))) {
+
+// Every public entry point: the context's device, and no single-scan tail left on the stream
+// unless the call is a single scan itself (keep_tail: its work is ordered after the tail).
+inline hipError_t enter(fbr_ctx* c, bool keep_tail = false) {
+  hipError_t e = hipSetDevice(c->dev);
+  if (e == hipSuccess && c->tail_pending && !keep_tail) {
+    e = fbr_sync(c->stream);
+    c->tail_pending = false;
+  }
+  return e;
+}
+
+// ---- functions that cross units, by the unit that defines them ----
+// (A unit defines them in namespace fbr::internal; they are hidden by their declaration here.
+// Everything else in a unit is file-local, in its anonymous namespace.)
+// fbr_api.hip
+void timer_begin(fbr_ctx* c, hipStream_t st, const char* name, hipEvent_t* ev_end);
+void timer_end(hipStream_t st, hipEvent_t ev_end);
+void feat_caps(int W, FeatArgs& a);
+// fbr_stages.hip
+Sub single_sub(fbr_ctx* c);
+int stage_project(fbr_ctx* c, const Sub& sb);
+int stage_features(fbr_ctx* c, const Sub& sb, bool stream_mode, bool err_clear = false, bool labels_out = false);
+int crop_stats(fbr_ctx* c, const Sub& sb);
+int register_prepare(fbr_ctx* c, const Sub& sb, bool trace);
+int stage_register(fbr_ctx* c, const Sub& sb, bool trace);
+void gn_run_start(fbr_ctx* c, GnRun& r, const Sub* subs, int nsub, bool trace);
+int gn_run_pass(fbr_ctx* c, GnRun& r, bool block, bool* progress);
+int advance_runs(fbr_ctx* c, int target);
+int batch_quiesce(fbr_ctx* c);
+int copy_results(fbr_ctx* c, int B, fbr_reg_stats* stats, float* poses_out, bool with_reg = true, int64_t w0 = 0,
+                 bool per_job = false);
+int check_err(fbr_ctx* c, int B);
+// fbr_batch.hip
+int drop_staged_batch(fbr_ctx* c);
+// fbr_map.hip
+int voxel_grid_dev(fbr_ctx* c, const float4* d_in, int64_t n, float leaf, float4* d_out, int64_t* n_out);
+
+}  // namespace internal
+}  // namespace fbr
+
+// Kernel launch timed by its dispatches' own start / end timestamps (when profiling).
+#define TIMED_ON(ctx, st, name, launch)   \
+  do {                                    \
+    hipEvent_t ev_;                       \
+    timer_begin(ctx, st, name, &ev_);     \
+    launch;                               \
+    timer_end(st, ev_);                   \
+  } while (0)
+#define TIMED(ctx, name, launch) TIMED_ON(ctx, (ctx)->stream, name, launch)

@@ -11,6 +11,7 @@
 #include "fbr_common.h"
 #include "fbr_imu.h"
 #include "fbr_kernels.h"
+#include "fbr_knobs.h"
 #include "fbr_solvers.h"
 
 namespace fbr {
@@ -884,22 +885,8 @@ void launch_gn_knn_rl(hipStream_t s, const GnArgs& a, int grid, int use_prev) {
 // Lanes per query of the plain kNN pass (FBR_KNN_LPQ = 1 or 8; default 8 for sub-batches of at
 // most 2 jobs, where one lane per query leaves the chip idle and the launch is one query's chain).
 inline int knn_lpq(int jobs) {
-  static const int forced = [] {
-    const char* e = std::getenv("FBR_KNN_LPQ");
-    return e ? (std::atoi(e) >= 8 ? 8 : 1) : 0;
-  }();
-  if (forced) return forced;
+  if (const int forced = knobs::knn_lpq()) return forced;
   return jobs <= 2 ? 8 : 1;
-}
-
-// Flat row queue (FBR_KNN_FLAT=0 disables): from iteration 1 on (warm-start bound), 1 m y/z cells
-// (9 rows: the queue is 18 KB of LDS per workgroup), not in the fused tail launch.
-inline bool knn_flat() {
-  static const bool v = [] {
-    const char* e = std::getenv("FBR_KNN_FLAT");
-    return e ? std::atoi(e) != 0 : true;
-  }();
-  return v;
 }
 
 template <int R, bool F>
@@ -910,7 +897,7 @@ void launch_gn_knn_r(hipStream_t s, const GnArgs& a, int grid, int use_prev) {
   // flat queue for the 1 m cells from iteration 1 (round 4 measured it slower in iteration 0, with
   // no warm-start bound, and for the 0.5 m cells, whose 25-row queue costs occupancy)
   if constexpr (R == 1 && !F) {
-    if (use_prev && knn_flat()) return launch_gn_knn_rl<R, F, true>(s, a, grid, use_prev);
+    if (use_prev && knobs::knn_flat()) return launch_gn_knn_rl<R, F, true>(s, a, grid, use_prev);
   }
   launch_gn_knn_rl<R, F, false>(s, a, grid, use_prev);
 }

@@ -12,7 +12,7 @@
 namespace fbr {
 
 // ---- kernel timing (fbr_set_profiling) ----
-// When a launcher runs under a kernel timer (fbr_api.hip TIMED_ON), its kernels are dispatched with
+// When a launcher runs under a kernel timer (fbr_ctx.h TIMED_ON), its kernels are dispatched with
 // hipExtLaunchKernel and the timer's events: the first kernel's dispatch records the start event
 // with its own start timestamp and every kernel records the stop event with its end timestamp, so
 // the measured interval is the launcher's kernels' execution (the timestamps rocprofv3's kernel
@@ -230,7 +230,7 @@ inline void arena_free(DevArena& a) {
 }
 
 // One large cloud on the whole device (rocprim stable radix sort); *d_nout gets the voxel count.
-constexpr int64_t kVgLargeMin = 32768;  // below this the one-workgroup kernel is faster
+// (Callers take it from knobs::vg_large_min() points on: below, the one-workgroup kernel is faster.)
 int voxel_grid_large(hipStream_t s, DevArena& ar, const float4* in, int64_t n, float leaf, int morton, int exact,
                      float4* out, int32_t* d_nout);
 

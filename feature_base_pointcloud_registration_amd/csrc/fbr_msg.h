@@ -1,5 +1,5 @@
 // fbr_msg.h — internal: PointCloud2 -> PointXYZIRT field mapping shared by the host converter
-// (fbr_msg.cpp) and the device unpack path (fbr_api.hip / k_project.hip).
+// (fbr_msg.cpp) and the device unpack path (fbr_scan.hip / k_project.hip).
 #pragma once
 #include <cstdint>
 

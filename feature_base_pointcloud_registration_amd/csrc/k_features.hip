@@ -34,6 +34,7 @@
 // candidates (label <= 0, index order) are read from the mask by the per-ring VoxelGrid.
 #include "fbr_common.h"
 #include "fbr_kernels.h"
+#include "fbr_knobs.h"
 #include "fbr_sort.h"
 
 #include <algorithm>
@@ -1373,12 +1374,7 @@ size_t features_gslot_bytes(const FeatArgs& a) {
 // Waves per ring: FBR_FEAT_WAVES (1, 2 or 4) or, by default, 4 while a launch has at most 2048
 // rings (<= 2 rings per SIMD: single scans, small sub-batches), 1 above.
 int feature_waves(int rings) {
-  static const int forced = [] {
-    const char* e = std::getenv("FBR_FEAT_WAVES");
-    const int v = e ? std::atoi(e) : 0;
-    return v >= 4 ? 4 : v >= 2 ? 2 : v == 1 ? 1 : 0;
-  }();
-  if (forced) return forced;
+  if (const int forced = knobs::feat_waves()) return forced;
   return rings <= 2048 ? 4 : 1;
 }
 

@@ -29,6 +29,7 @@
 
 #include "fbr_common.h"
 #include "fbr_kernels.h"
+#include "fbr_knobs.h"
 
 namespace fbr {
 
@@ -166,16 +167,6 @@ void free_grid(DevGrid& d) {
   d = DevGrid{};
 }
 
-namespace {
-bool force_sparse_env() {
-  static const bool v = [] {
-    const char* e = std::getenv("FBR_GRID_SPARSE");
-    return e ? std::atoi(e) != 0 : false;
-  }();
-  return v;
-}
-}  // namespace
-
 int grid_build_device(hipStream_t s, DevArena& ar, const float4* src, int64_t n, float invx, float inv,
                       bool force_sparse, DevGrid& out) {
   free_grid(out);
@@ -214,7 +205,7 @@ int grid_build_device(hipStream_t s, DevArena& ar, const float4* src, int64_t n,
   // product so that far outliers on every axis cannot overflow it
   const bool too_big = dims[0] > kDenseGridCells || dims[1] > kDenseGridCells / dims[0] ||
                        dims[2] > kDenseGridCells / (dims[0] * dims[1]);
-  const bool sparse = force_sparse || force_sparse_env() || too_big;
+  const bool sparse = force_sparse || knobs::grid_sparse() || too_big;
   if (sparse && (dims[0] > ((int64_t)1 << 28) || dims[1] > ((int64_t)1 << 24) || dims[2] > ((int64_t)1 << 12)))
     return FBR_ERR_CAPACITY;
   for (int d = 0; d < 3; ++d) g.dims[d] = (int32_t)std::min<int64_t>(dims[d], INT32_MAX);

@@ -8,7 +8,7 @@
 //   transformPointCloud() :405-425  pcl::getTransformation(x, y, z, roll, pitch, yaw) in float,
 //                                    rows ((r0 x + r1 y) + r2 z) + t
 // The keyframe selection (extractNearby / extractForLoopClosure, :857-907) is a serial pass over
-// a few hundred key poses and runs on the host (fbr_api.hip).
+// a few hundred key poses and runs on the host (fbr_map.hip).
 //
 // k_kf_transform: one workgroup per (selected entry, 1024-point chunk); each entry is a copy of
 // one keyframe's cloud into its concatenation offset, transformed by that keyframe's pose.

@@ -397,20 +397,10 @@ __global__ void __launch_bounds__(256) k_gn_knn_list(GnArgs a, int iter) {
   }
 }
 
-// FBR_KNN_TILE: 1 serves iterations >= 1 on dense 0.5 m x 0.125 m grids from the block tiles; 0
-// (the default: the tiles measured slower than the grid search) keeps the grid
-// search for every query.
-bool knn_tile_enabled() {
-  static const bool v = [] {
-    const char* e = std::getenv("FBR_KNN_TILE");
-    return e ? std::atoi(e) != 0 : false;
-  }();
-  return v;
-}
-
-// The tiles apply to dense grids of 0.5 m y/z x 0.125 m x cells (the k_gn_knn<2, 8> layout).
+// The tiles apply to dense grids of 0.5 m y/z x 0.125 m x cells (the k_gn_knn<2, 8> layout), when
+// FBR_KNN_TILE turns them on.
 bool knn_tile_applies(const GridDesc& gc, const GridDesc& gs) {
-  return knn_tile_enabled() && !gc.sparse && !gs.sparse && gc.inv_x == 8.0f && gc.inv_cell == 2.0f &&
+  return knobs::knn_tile() && !gc.sparse && !gs.sparse && gc.inv_x == 8.0f && gc.inv_cell == 2.0f &&
          gs.inv_x == 8.0f && gs.inv_cell == 2.0f;
 }
 
@@ -438,8 +428,7 @@ bool launch_gn_knn_tile(hipStream_t s, const GnArgs& a, int grid, int iter) {
 // Diagnostic counters (FBR_KNN_TILE_STATS=1): allocated once, null otherwise.
 unsigned long long* knn_tile_stats_buffer() {
   static unsigned long long* p = [] {
-    const char* e = std::getenv("FBR_KNN_TILE_STATS");
-    if (!e || std::atoi(e) == 0) return (unsigned long long*)nullptr;
+    if (!knobs::knn_tile_stats()) return (unsigned long long*)nullptr;
     unsigned long long* q = nullptr;
     if (hipMalloc(&q, sizeof(unsigned long long) * 8) != hipSuccess) return (unsigned long long*)nullptr;
     if (hipMemset(q, 0, sizeof(unsigned long long) * 8) != hipSuccess) return (unsigned long long*)nullptr;

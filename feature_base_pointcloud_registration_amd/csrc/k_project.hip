@@ -25,6 +25,7 @@
 #include "fbr_fdlibm.h"
 #include "fbr_imu.h"
 #include "fbr_kernels.h"
+#include "fbr_knobs.h"
 
 namespace fbr {
 
@@ -519,24 +520,11 @@ void launch_project(hipStream_t s, const fbr_point_xyzirt* pts, const int64_t* n
                tile_log2, owner, err, n_single, ot);
 }
 
-// Compaction tile size in cells (FBR_COMPACT_CELLS: 512, 1024 or 2048).  512 since round 5: 10 KB of
-// LDS per workgroup, twice the tiles in flight per CU; once the other kernels had shrunk, C2 B = 1024
-// 114.5-114.9k -> 115.7-115.8k and C3 +0.9 % interleaved (profiles/r05ar_compact_cells_ab.txt; it was
-// even with 1024 in round 4).
-int compact_cells() {
-  static const int v = [] {
-    const char* e = std::getenv("FBR_COMPACT_CELLS");
-    const int c = e ? std::atoi(e) : 512;
-    return c >= 2048 ? 2048 : c >= 1024 ? 1024 : 512;
-  }();
-  return v;
-}
-
 void launch_extract(hipStream_t s, const fbr_point_xyzirt* pts, int64_t nmax, int32_t* owner, int B, int H,
                     int W, int32_t* rowcnt, int32_t* choff, float4* cloud, int32_t* col, float* range,
                     int32_t* start_ring, int32_t* end_ring, int32_t* nvalid, const DeskArgs& desk, const float4* pk,
                     const OwnerTag& ot) {
-  const CompactTile T = compact_tile(H, compact_cells());
+  const CompactTile T = compact_tile(H, knobs::compact_cells());
   fbr_launch(k_rowcount, dim3(H, B), dim3(64), 0, s, owner, H, W, T.cg, rowcnt, desk.mode ? desk.rowmin : nullptr,
              choff, ot);
   const int tiles = ((H + T.hb - 1) / T.hb) * compact_nchunk(T.cg, W);

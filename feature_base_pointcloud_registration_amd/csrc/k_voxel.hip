@@ -28,6 +28,7 @@
 #include "fbr_common.h"
 #include "fbr_introsort.h"
 #include "fbr_kernels.h"
+#include "fbr_knobs.h"
 
 #include <algorithm>
 #include <atomic>
@@ -1539,15 +1540,6 @@ void launch_voxel_ring(hipStream_t s, const VgRing& a) {
   }
 }
 
-// In-place LDS sort of the mapping-DS segments (FBR_VG_INPLACE=0: the global-scratch kernel).
-bool vg_inplace() {
-  static const bool v = [] {
-    const char* e = std::getenv("FBR_VG_INPLACE");
-    return e ? std::atoi(e) != 0 : true;
-  }();
-  return v;
-}
-
 size_t voxel_lds_bytes(const VgArgs& a, int threads, bool lds_mode) {
   const int nw = threads / 64;
   size_t b = sizeof(uint32_t) * ((size_t)(nw + 1) * 512 + nw) + sizeof(float) * nw * 6 + sizeof(int) * 4;
@@ -1571,25 +1563,9 @@ constexpr int kVgIpKpl = 18;  // k_voxel_grid_ip: segments up to 1024 * 18 point
 // first (default), 2 = last.
 constexpr int kVgIpSmallT = 256, kVgIpSmallKpl = 16;
 constexpr int64_t kVgIpSmallSetCap = 4 * kVgIpSmallT * kVgIpSmallKpl;
-int vg_classes() {
-  static const int v = [] {
-    const char* e = std::getenv("FBR_VG_CLASSES");
-    const int c = e ? std::atoi(e) : 1;
-    return c < 0 || c > 2 ? 1 : c;
-  }();
-  return v;
-}
 constexpr int kVgSplitSlots = 16;   // k_voxel_grid_split: segments x parts per launch
 constexpr int kVgSplitRing = 1024;  // flag regions: a launch's own region (concurrent launches)
 constexpr int kVgSplitMaxDevices = 64;
-int vg_split() {
-  static const int v = [] {
-    const char* e = std::getenv("FBR_VG_SPLIT");
-    const int p = e ? std::atoi(e) : 8;
-    return p < 2 ? 1 : std::min(p, 8);
-  }();
-  return v;
-}
 
 void launch_voxel_grid(hipStream_t s, const VgArgs& a) {
   const int nseg = a.s[0].nseg + a.s[1].nseg;
@@ -1600,8 +1576,8 @@ void launch_voxel_grid(hipStream_t s, const VgArgs& a) {
   const bool exact = a.s[0].exact || a.s[1].exact;  // both sets share the context's mode
   // few segments (single-scan calls): P workgroups per segment (FBR_VG_SPLIT = P, default 8: C2 latency
   // -10 us against 4, profiles/r05w_latency_knob_sweep.txt; 1 off)
-  const int P = vg_split();
-  if (!exact && P > 1 && cap > kVgLdsCap && vg_inplace() && nseg * P <= kVgSplitSlots) {
+  const int P = knobs::vg_split();
+  if (!exact && P > 1 && cap > kVgLdsCap && knobs::vg_inplace() && nseg * P <= kVgSplitSlots) {
     // look-back flags of the current device (agent-scope atomics must stay on the device that runs
     // the kernel: contexts on several GPUs in one process each get their own)
     static std::mutex mu;
@@ -1632,13 +1608,13 @@ void launch_voxel_grid(hipStream_t s, const VgArgs& a) {
     constexpr bool E = decltype(ex)::value;
     if (cap <= kVgLdsCap) {
       fbr_launch((k_voxel_grid<256, uint16_t, true, E>), dim3(nseg), dim3(256), voxel_lds_bytes(a, 256, true), s, a);
-    } else if (vg_inplace()) {
+    } else if (knobs::vg_inplace()) {
       constexpr size_t pair = sizeof(uint32_t) + sizeof(uint16_t);
       const size_t lds = voxel_lds_bytes(a, 1024, false) + (size_t)1024 * kVgIpKpl * pair;
       // Two sets (the mapping DS of a batch: surf and corner clouds), one of them of the small
       // class: one launch per set, the instance by the set's own capacity.  Sets of one class
       // share a launch (two launches of one instance only serialise them on the stream).
-      const int cls = vg_classes();
+      const int cls = knobs::vg_classes();
       int small = -1;
       for (int k = 0; k < 2 && cls != 0; ++k)
         if (a.s[0].nseg > 0 && a.s[1].nseg > 0 && a.s[k].cap <= kVgIpSmallSetCap && a.s[k].cap < a.s[1 - k].cap) small = k;

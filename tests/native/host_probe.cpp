@@ -12,6 +12,7 @@
 
 #include "fbr_fdlibm.h"
 #include "fbr_icp_solve.h"
+#include "fbr_knobs.h"
 #include "fbr_sincosf.h"
 #include "fbr_sort.h"
 
@@ -67,6 +68,53 @@ void probe_sort(const float* values, int64_t n, int64_t* ind_out) {
 // the row-major 3x4 float T of each.
 void probe_icp_umeyama(const double* sums, float* T, int64_t n) {
   for (int64_t i = 0; i < n; ++i) fbr::icp_umeyama(sums + 17 * i, T + 12 * i);
+}
+
+// Every environment knob (fbr_knobs.h) as this process's environment gives it, in header order.
+// The two cell sizes go out as 8 / metres (their inverse cell times 8), for mapping leaves of at
+// least 0.3 m; the same two for smaller leaves follow the last knob.  Returns the count written.
+int64_t probe_knobs(int64_t* out) {
+  namespace k = fbr::knobs;
+  int64_t n = 0;
+  out[n++] = k::nsub(8);
+  out[n++] = k::knn_tile();
+  out[n++] = k::knn_tile_stats();
+  out[n++] = k::vg_split();
+  out[n++] = k::ingest_compact();
+  out[n++] = k::copy_spin_us();
+  out[n++] = k::compact_cells();
+  out[n++] = k::gn_grid_cap();
+  out[n++] = k::gn_one_item();
+  out[n++] = k::gn_tail_one_item();
+  out[n++] = k::gn_one_grid();
+  out[n++] = k::packed_scans();
+  out[n++] = k::feat_compact();
+  out[n++] = k::feat_surf_win();
+  out[n++] = k::feat_surf_window();
+  out[n++] = k::owner_tags();
+  out[n++] = k::owner_tmax();
+  out[n++] = k::gn_tail_div();
+  out[n++] = k::gn_lag();
+  out[n++] = k::knn_flat();
+  out[n++] = (int64_t)(8.0f * k::knn_cell_inv(true));
+  out[n++] = (int64_t)(8.0f * k::knn_cell_x_inv(true));
+  out[n++] = k::vg_large_min();
+  out[n++] = k::vr_dbg();
+  out[n++] = k::vg_inplace();
+  out[n++] = k::vg_classes();
+  out[n++] = k::fit_cache();
+  out[n++] = k::grid_sparse();
+  out[n++] = k::knn_lpq();
+  out[n++] = k::feat_waves();
+  out[n++] = k::direct_results();
+  out[n++] = k::pinned_upload();
+  out[n++] = k::stage_mb();
+  out[n++] = k::stage_threads();
+  out[n++] = k::ingest_xstream();
+  out[n++] = k::ingest_nt();
+  out[n++] = (int64_t)(8.0f * k::knn_cell_inv(false));
+  out[n++] = (int64_t)(8.0f * k::knn_cell_x_inv(false));
+  return n;
 }
 
 }

@@ -423,7 +423,7 @@ def test_process_batch_drops_out_of_range_rings_like_staged_path(c2_map):
 @pytest.mark.parametrize("h_extra", [0, 200])
 def test_process_batch_ragged_scans_match_staged_path(c2_map, h_extra):
     """The packers write 16-point groups with streaming stores and the rest one point at a time,
-    into 16-B aligned planes (fbr_api.hip pack_compact): scans of every length mod 16, a 5-point
+    into 16-B aligned planes (fbr_batch.hip pack_compact): scans of every length mod 16, a 5-point
     scan and an empty one give fbr_batch_stage's results bit for bit.  h_extra = 200 declares 264
     rings, so the rings ship as u16 (rb = 2)."""
     H, W = synth.CONFIGS["C2"][:2]
@@ -484,7 +484,7 @@ def test_batch_full_masks_match_oracle_labels(cfg, nj):
 
 def test_batch_tail_mode_matches_oracle(c2_map):
     """24 jobs = 3 sub-batches of 8: each sub-batch's last iterating job runs its final Gauss-Newton
-    iterations in tail mode (fused kNN + residual launch, fbr_api.hip gn_tail_div); every pose and
+    iterations in tail mode (fused kNN + residual launch, fbr_knobs.h gn_tail_div); every pose and
     iteration count still matches the oracle."""
     H, W = synth.CONFIGS["C2"][:2]
     B = 24

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round-6 first look: the GPU suite, then the default C2 B=1024 line (x2) interleaved with
-# FBR_GN_FUSED=1 (x2) and the round-5 library (prev), then the exact_voxel_order=1 main line at
+# the round-5 library (prev), then the exact_voxel_order=1 main line at
 # B=1024 with its per-kernel times.
 set -o pipefail
 export TMPDIR=/tmp
@@ -15,8 +15,6 @@ PKG=$PWD/feature_base_pointcloud_registration_amd
 for r in 1 2; do
   timeout -k 10 300 python3 $B > $OUT/def_$r.json 2> $OUT/def_$r.err || { tail $OUT/def_$r.err; exit 11; }
   summ $OUT/def_$r.json "default $r"
-  FBR_GN_FUSED=1 timeout -k 10 300 python3 $B > $OUT/fused_$r.json 2> $OUT/fused_$r.err || { tail $OUT/fused_$r.err; exit 12; }
-  summ $OUT/fused_$r.json "fused $r"
   FBR_LIB=$PKG/libfbr_hip_prev.so timeout -k 10 300 python3 $B > $OUT/prev_$r.json 2> $OUT/prev_$r.err || { tail $OUT/prev_$r.err; exit 13; }
   summ $OUT/prev_$r.json "prev(r05) $r"
 done
