@@ -188,6 +188,19 @@ def wait_stats(reset=False):
     return int(v[0]), int(v[1]), v[2] * 1e-9, int(v[3])
 
 
+def live_resources():
+    """What the process's contexts and communicators hold now: (device blocks, pinned blocks,
+    streams, events) -- diagnostic (fbr_diag_live_resources).  Back at its earlier value once they
+    are closed."""
+    if not hasattr(lib(), "fbr_diag_live_resources"):  # an A/B build of an earlier round (FBR_LIB)
+        return -1, -1, -1, -1
+    f = lib().fbr_diag_live_resources
+    f.restype, f.argtypes = ctypes.c_int, [_VP]
+    v = (ctypes.c_longlong * 4)()
+    _check(f(v), "fbr_diag_live_resources")
+    return tuple(int(x) for x in v)
+
+
 def batch_times(reset=False):
     """Host wall time (s) of fbr_batch_launch calls since the last reset, and the part of it spent
     waiting for the Gauss-Newton iteration flags -- diagnostic (fbr_diag_batch_times)."""

@@ -32,15 +32,16 @@ void timer_begin(fbr_ctx* c, hipStream_t st, const char* name, hipEvent_t* ev_en
   if (!c->profiling) return;
   if (!c->profile_only.empty() && c->profile_only.count(name) == 0) return;
   KernelTimer& t = c->timers[name];
-  std::pair<hipEvent_t, hipEvent_t> pr;
+  std::pair<Event, Event> own;
   if (!t.pool.empty()) {
-    pr = t.pool.back();
+    own = std::move(t.pool.back());
     t.pool.pop_back();
   } else {
-    (void)hipEventCreate(&pr.first);
-    (void)hipEventCreate(&pr.second);
+    (void)own.first.create(hipEventDefault);
+    (void)own.second.create(hipEventDefault);
   }
-  t.pending.push_back(pr);
+  const std::pair<hipEvent_t, hipEvent_t> pr(own.first, own.second);
+  t.pending.push_back(std::move(own));
   *ev_end = pr.second;
   // the launcher's kernels carry the events in their dispatches (fbr_launch, fbr_kernels.h)
   launch_timer() = LaunchTimer{pr.first, pr.second, 0};
@@ -153,15 +154,14 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
   // streams of the sub-batches this context can use, per slot (each stream takes a hardware queue:
   // unused ones are not created, so they cannot share a queue with a busy one)
   const int nstreams = std::max(2, c->nslot * c->nsub_pref);
-  bool sfail = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess;
-  for (int k = 0; k < nstreams && !sfail; ++k) {
-    if (k > 0) sfail = hipStreamCreateWithFlags(&c->xstream[k], hipStreamNonBlocking) != hipSuccess;
-    if (!sfail) sfail = hipEventCreateWithFlags(&c->xev[k], hipEventDisableTiming) != hipSuccess;
+  bool sok = c->stream.create(hipStreamNonBlocking);
+  for (int k = 0; k < nstreams && sok; ++k) {
+    if (k > 0) sok = c->xstream[k].create(hipStreamNonBlocking);
+    if (sok) sok = c->xev[k].create(hipEventDisableTiming);
   }
-  if (!sfail) sfail = hipEventCreateWithFlags(&c->ev_staged, hipEventDisableTiming) != hipSuccess ||
-                     hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                     hipEventCreateWithFlags(&c->ev_ext, hipEventDisableTiming) != hipSuccess;
-  if (sfail) {
+  sok = sok && c->ev_staged.create(hipEventDisableTiming) && c->ev_fork.create(hipEventDisableTiming) &&
+        c->ev_ext.create(hipEventDisableTiming);
+  if (!sok) {
     fbr_destroy(c);
     return FBR_ERR_HIP;
   }
@@ -169,45 +169,40 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
   c->max_items = (int)(Bw * c->items_per_job);
   c->vg_scratch_elems = kVgScratch * Bw * (HW + std::min<int64_t>(HW, (int64_t)kCornerPerRing * H));
   // inputs: B jobs; work arrays: Bw jobs (nslot launch slots)
-  bool fail = dalloc(&c->d_pts, B * c->NMAX) || dalloc(&c->d_nin, B) || dalloc(&c->d_guess, B * 6) ||
-              dalloc(&c->d_owner, Bw * HW) || dalloc(&c->d_rowcnt, Bw * H) || dalloc(&c->d_col, Bw * HW) ||
-              dalloc(&c->d_start, Bw * H) || dalloc(&c->d_end, Bw * H) || dalloc(&c->d_nvalid, Bw) ||
-              dalloc(&c->d_cloud, Bw * HW) || dalloc(&c->d_range, Bw * HW) || dalloc(&c->d_sstate, Bw) ||
-              dalloc(&c->d_sstream, 1) || dalloc(&c->d_label, Bw * HW) || dalloc(&c->d_label_stream, HW) ||
-              dalloc(&c->d_corner_slot, Bw * H * kCornerPerRing) || dalloc(&c->d_corner_cnt, Bw * H) ||
-              dalloc(&c->d_surf_ring, Bw * HW) ||
-              dalloc(&c->d_surf_ring_cnt, Bw * H) || dalloc(&c->d_ring_box, Bw * H * kRingBox) || dalloc(&c->d_err, Bw) ||
-              dalloc(&c->d_corner_all, Bw * HW) ||
-              dalloc(&c->d_surf_all, Bw * HW) || dalloc(&c->d_cornerDS, Bw * HW) || dalloc(&c->d_surfDS, Bw * HW) ||
-              dalloc(&c->d_ncorner, Bw) || dalloc(&c->d_nsurf, Bw) || dalloc(&c->d_ncds, Bw) || dalloc(&c->d_nsds, Bw) ||
-              dalloc(&c->d_vg_scratch, c->vg_scratch_elems) ||
-              dalloc(&c->d_gn, Bw) || dalloc(&c->d_items, c->max_items) || dalloc(&c->d_nitems, kMaxSub) ||
-              dalloc(&c->d_item_range, 2 * Bw) || dalloc(&c->d_cropcnt, 2 * B) || dalloc(&c->d_cropwork, 2 * Bw) ||
-              dalloc(&c->d_partial, (int64_t)c->max_items * 32) ||
-              dalloc(&c->d_nbr, (int64_t)c->max_items * 5 * 256) ||
-              dalloc(&c->d_fitc, (int64_t)c->max_items * 6 * 256) || dalloc(&c->d_fits, (int64_t)c->max_items * 256) ||
-              dalloc(&c->d_nsame, (int64_t)c->max_items * 256) ||
-              dalloc(&c->d_iter_cnt, kMaxSub * 4 * std::max(1, p->max_iterations)) ||
-              dalloc(&c->d_feat_scratch, Bw * H * feat_slot_bytes(c->W)) ||
-              hipHostMalloc((void**)&c->h_iter_flags, sizeof(unsigned long long) * kMaxSub * (std::max(1, p->max_iterations) + 1),
-                            hipHostMallocMapped) != hipSuccess ||
-              hipHostGetDevicePointer((void**)&c->d_iter_flags, c->h_iter_flags, 0) != hipSuccess || dalloc(&c->d_pose_out, Bw * 6) ||
-              dalloc(&c->d_stats, Bw) || dalloc(&c->d_trace, Bw * p->max_iterations * 6) ||
-              dalloc(&c->d_desk_mode, B) || dalloc(&c->d_rowmin, Bw * H) || dalloc(&c->d_result, B) ||
-              dalloc(&c->d_choff, Bw * H * (c->W / 32 + 1)) ||
-              hipHostMalloc((void**)&c->h_result, sizeof(JobResult) * B, hipHostMallocDefault) != hipSuccess ||
-              hipHostMalloc((void**)&c->h_scan, sizeof(fbr_point_xyzirt) * std::max<int64_t>(c->NMAX, 1),
-                            hipHostMallocDefault) != hipSuccess ||
-              hipHostMalloc((void**)&c->h_nin, sizeof(int64_t), hipHostMallocDefault) != hipSuccess ||
-              hipHostMalloc((void**)&c->h_crop, sizeof(int32_t) * 2, hipHostMallocDefault) != hipSuccess ||
-              hipHostMalloc((void**)&c->h_guess, sizeof(float) * 6, hipHostMallocDefault) != hipSuccess ||
-              hipHostMalloc((void**)&c->h_direct, sizeof(JobResult), hipHostMallocMapped) != hipSuccess ||
+  bool fail = dalloc(c->d_pts_own, B * c->NMAX) || dalloc(c->d_nin, B) || dalloc(c->d_guess, B * 6) ||
+              dalloc(c->d_owner, Bw * HW) || dalloc(c->d_rowcnt, Bw * H) || dalloc(c->d_col, Bw * HW) ||
+              dalloc(c->d_start, Bw * H) || dalloc(c->d_end, Bw * H) || dalloc(c->d_nvalid, Bw) ||
+              dalloc(c->d_cloud, Bw * HW) || dalloc(c->d_range, Bw * HW) || dalloc(c->d_sstate, Bw) ||
+              dalloc(c->d_sstream, 1) || dalloc(c->d_label, Bw * HW) || dalloc(c->d_label_stream, HW) ||
+              dalloc(c->d_corner_slot, Bw * H * kCornerPerRing) || dalloc(c->d_corner_cnt, Bw * H) ||
+              dalloc(c->d_surf_ring, Bw * HW) ||
+              dalloc(c->d_surf_ring_cnt, Bw * H) || dalloc(c->d_ring_box, Bw * H * kRingBox) || dalloc(c->d_err, Bw) ||
+              dalloc(c->d_corner_all, Bw * HW) ||
+              dalloc(c->d_surf_all, Bw * HW) || dalloc(c->d_cornerDS, Bw * HW) || dalloc(c->d_surfDS, Bw * HW) ||
+              dalloc(c->d_ncorner, Bw) || dalloc(c->d_nsurf, Bw) || dalloc(c->d_ncds, Bw) || dalloc(c->d_nsds, Bw) ||
+              dalloc(c->d_vg_scratch, c->vg_scratch_elems) ||
+              dalloc(c->d_gn, Bw) || dalloc(c->d_items, c->max_items) || dalloc(c->d_nitems, kMaxSub) ||
+              dalloc(c->d_item_range, 2 * Bw) || dalloc(c->d_cropcnt, 2 * B) || dalloc(c->d_cropwork, 2 * Bw) ||
+              dalloc(c->d_partial, (int64_t)c->max_items * 32) ||
+              dalloc(c->d_nbr, (int64_t)c->max_items * 5 * 256) ||
+              dalloc(c->d_fitc, (int64_t)c->max_items * 6 * 256) || dalloc(c->d_fits, (int64_t)c->max_items * 256) ||
+              dalloc(c->d_nsame, (int64_t)c->max_items * 256) ||
+              dalloc(c->d_iter_cnt, kMaxSub * 4 * std::max(1, p->max_iterations)) ||
+              dalloc(c->d_feat_scratch, Bw * H * feat_slot_bytes(c->W)) ||
+              dalloc(c->h_iter_flags, kMaxSub * (std::max(1, p->max_iterations) + 1)) ||
+              hipHostGetDevicePointer((void**)&c->d_iter_flags, c->h_iter_flags, 0) != hipSuccess || dalloc(c->d_pose_out, Bw * 6) ||
+              dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6) ||
+              dalloc(c->d_desk_mode, B) || dalloc(c->d_rowmin, Bw * H) || dalloc(c->d_result, B) ||
+              dalloc(c->d_choff, Bw * H * (c->W / 32 + 1)) ||
+              dalloc(c->h_result, B) || dalloc(c->h_scan, c->NMAX) || dalloc(c->h_nin, 1) || dalloc(c->h_crop, 2) ||
+              dalloc(c->h_guess, 6) || dalloc(c->h_direct, 1) ||
               hipHostGetDevicePointer((void**)&c->d_direct, c->h_direct, 0) != hipSuccess ||
-              dalloc(&c->d_direct_done, 1);
+              dalloc(c->d_direct_done, 1);
   if (fail) {
     fbr_destroy(c);
     return FBR_ERR_HIP;
   }
+  c->d_pts = c->d_pts_own;
   std::memset(c->h_iter_flags, 0, sizeof(unsigned long long) * kMaxSub * (std::max(1, p->max_iterations) + 1));
   std::memset(c->h_direct, 0, sizeof(JobResult));
   if (hipMemset(c->d_sstream, 0, sizeof(StreamState)) != hipSuccess ||
@@ -231,65 +226,12 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
 int fbr_destroy(fbr_ctx* c) {
   if (!c) return FBR_ERR_INVALID_ARG;
   (void)hipSetDevice(c->dev);
+  // drain every stream; ~fbr_ctx then releases the buffers before the streams and events
   if (c->stream) (void)fbr_sync(c->stream);
   for (int k = 1; k < kMaxSub; ++k)
     if (c->xstream[k]) (void)fbr_sync(c->xstream[k]);
-  void* ptrs[] = {c->d_pts, c->d_nin, c->d_guess, c->d_owner, c->d_rowcnt, c->d_col, c->d_start, c->d_end,
-                  c->d_nvalid, c->d_cloud, c->d_range, c->d_sstate, c->d_sstream, c->d_label, c->d_label_stream,
-                  c->d_corner_slot, c->d_corner_cnt, c->d_surf_ring, c->d_surf_ring_cnt, c->d_ring_box,
-                  c->d_err, c->d_corner_all, c->d_surf_all, c->d_cornerDS, c->d_surfDS, c->d_ncorner, c->d_nsurf,
-                  c->d_ncds, c->d_nsds, c->d_vg_scratch, c->d_gn, c->d_items, c->d_nitems,
-                  c->d_item_range, c->d_cropcnt, c->d_cropwork, c->d_partial, c->d_pose_out, c->d_stats, c->d_trace, c->d_nbr, c->d_fitc, c->d_fits, c->d_nsame, c->d_fb_list, c->d_bin, c->d_iter_cnt, c->d_feat_scratch, c->d_msg,
-                  c->d_desk, c->d_desk_mode, c->d_rowmin, c->d_choff,
-                  c->d_kf_c, c->d_kf_s, c->d_kraw_c, c->d_kraw_s, c->d_kds_c, c->d_kds_s, c->d_kf_segs, c->d_bounds, c->d_direct_done, c->d_pk,
-                  c->d_icp_src, c->d_icp_x, c->d_icp_raw, c->d_icp_tgt, c->d_icp_key, c->d_icp_far, c->d_icp_partial,
-                  c->d_icp_segs, c->d_icp_state};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (c->d_feat_paths) (void)hipFree(c->d_feat_paths);
-  if (c->h_iter_flags) (void)hipHostFree(c->h_iter_flags);
-  free_grid(c->grid_c);
-  free_grid(c->grid_s);
-  free_grid(c->icp_grid);
-  if (c->h_icp_flag) (void)hipHostFree(c->h_icp_flag);
-  arena_free(c->arena);
-  for (void* h : {(void*)c->h_result, (void*)c->h_scan, (void*)c->h_nin, (void*)c->h_msg, (void*)c->h_crop, (void*)c->h_guess,
-                  (void*)c->h_direct})
-    if (h) (void)hipHostFree(h);
-  if (c->d_result) (void)hipFree(c->d_result);
   if (c->ing.cstream) (void)fbr_sync(c->ing.cstream);
   if (c->ing.xstream) (void)fbr_sync(c->ing.xstream);
-  if (c->ing.h_stage) (void)hipHostFree(c->ing.h_stage);
-  if (c->ing.d_pts_slot[1]) (void)hipFree(c->ing.d_pts_slot[1]);
-  for (uint8_t* d : c->ing.d_stage)
-    if (d) (void)hipFree(d);
-  if (c->ing.copied_ev) (void)hipEventDestroy(c->ing.copied_ev);
-  if (c->ing.d_nin) (void)hipFree(c->ing.d_nin);
-  if (c->ing.h_nin) (void)hipHostFree(c->ing.h_nin);
-  for (auto& e : c->ing.up_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->ing.chunk_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (c->ing.cstream) (void)hipStreamDestroy(c->ing.cstream);
-  if (c->ing.xstream) (void)hipStreamDestroy(c->ing.xstream);
-  for (auto& kv : c->timers) {
-    for (auto& pr : kv.second.pending) {
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
-    for (auto& pr : kv.second.pool) {
-      (void)hipEventDestroy(pr.first);
-      (void)hipEventDestroy(pr.second);
-    }
-  }
-  if (c->stream) (void)hipStreamDestroy(c->stream);
-  for (int k = 0; k < kMaxSub; ++k) {
-    if (c->xstream[k]) (void)hipStreamDestroy(c->xstream[k]);
-    if (c->xev[k]) (void)hipEventDestroy(c->xev[k]);
-  }
-  if (c->ev_staged) (void)hipEventDestroy(c->ev_staged);
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->ev_ext) (void)hipEventDestroy(c->ev_ext);
   delete c;
   return FBR_OK;
 }
@@ -342,6 +284,15 @@ extern "C" int fbr_diag_batch_times(long long* out2, int reset) {
   return FBR_OK;
 }
 
+// Diagnostic: what the process's contexts and communicators hold now: [0] device blocks, [1] pinned
+// blocks, [2] streams, [3] events (fbr_own.h's handles; the kernels' per-device statics, the grids,
+// the arena and the copy pool are not counted).  Back at its earlier value once they are destroyed.
+extern "C" int fbr_diag_live_resources(long long out[4]) {
+  if (!out) return FBR_ERR_INVALID_ARG;
+  for (int k = 0; k < own::kLiveKinds; ++k) out[k] = own::live(k).load(std::memory_order_relaxed);
+  return FBR_OK;
+}
+
 // Diagnostic: the per-ring surf filter kernel of this context's default-order launches: -1 by
 // launch size (four waves per ring above 256 rings, else the 512-thread kernel), 0 the 512-thread
 // kernel, 2 four waves per ring -- so a test can compare the two on the same scans.
@@ -367,7 +318,7 @@ extern "C" int fbr_diag_feature_stamps(fbr_ctx* c, unsigned long long* out /* [m
   CK(enter(c));
   const size_t n = (size_t)c->Bwork * c->H * 12;  // both launch slots (the first launch uses slot 0)
   if (!c->d_feat_stamps) {
-    CK(hipMalloc(&c->d_feat_stamps, sizeof(unsigned long long) * n));
+    if (dalloc(c->d_feat_stamps, n)) return FBR_ERR_HIP;
     CK(hipMemset(c->d_feat_stamps, 0, sizeof(unsigned long long) * n));
     return FBR_OK;
   }
@@ -384,7 +335,7 @@ extern "C" int fbr_diag_feature_paths(fbr_ctx* c, uint32_t* out, int64_t cap, in
   const size_t n = (size_t)c->Bwork * c->H;
   if (n_out) *n_out = (int64_t)n;
   if (!c->d_feat_paths) {
-    CK(hipMalloc(&c->d_feat_paths, sizeof(uint32_t) * n));
+    if (dalloc(c->d_feat_paths, n)) return FBR_ERR_HIP;
     CK(hipMemset(c->d_feat_paths, 0, sizeof(uint32_t) * n));
     return FBR_OK;
   }
@@ -429,15 +380,22 @@ int fbr_kernel_time(fbr_ctx* c, const char* kernel, double* total_ms, int64_t* l
     return FBR_OK;
   }
   KernelTimer& t = itr->second;
-  for (auto& pr : t.pending) {
-    CK(hipEventSynchronize(pr.second));
+  size_t done = 0;  // pairs read and moved to the pool; they leave `pending` on every path
+  int rc = FBR_OK;
+  for (; done < t.pending.size(); ++done) {
+    std::pair<Event, Event>& pr = t.pending[done];
     float ms = 0.0f;
-    CK(hipEventElapsedTime(&ms, pr.first, pr.second));
+    if (!hip_ok(hipEventSynchronize(pr.second), "fbr_kernel_time") ||
+        !hip_ok(hipEventElapsedTime(&ms, pr.first, pr.second), "fbr_kernel_time")) {
+      rc = FBR_ERR_HIP;
+      break;
+    }
     t.total_ms += ms;
     t.launches += 1;
-    t.pool.push_back(pr);
+    t.pool.push_back(std::move(pr));
   }
-  t.pending.clear();
+  t.pending.erase(t.pending.begin(), t.pending.begin() + done);
+  if (rc) return rc;
   if (total_ms) *total_ms = t.total_ms;
   if (launches) *launches = t.launches;
   return FBR_OK;

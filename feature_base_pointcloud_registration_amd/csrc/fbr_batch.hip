@@ -49,7 +49,7 @@ int fbr_batch_stage(fbr_ctx* c, const fbr_point_xyzirt* const* scans, const int6
   // scans, whose time deskewPoint reads.
   const bool pk = knobs::packed_scans() && !c->desk_any;
   if (pk) {
-    if (!c->d_pk && dalloc(&c->d_pk, (int64_t)c->Bcap * c->NMAX)) return FBR_ERR_HIP;
+    if (!c->d_pk && dalloc(c->d_pk, (int64_t)c->Bcap * c->NMAX)) return FBR_ERR_HIP;
     std::vector<float4> rec;
     for (int j0 = 0; j0 < n_jobs && !rc; j0 += 64) {  // 64 scans per host buffer (~118 MB for C2)
       const int j1 = std::min(n_jobs, j0 + 64);
@@ -116,7 +116,7 @@ int fbr_set_deskew(fbr_ctx* c, const fbr_deskew_table* tables, int n_tables) {
     mode[j] = tables[j].imu_available ? (kDeskPoints | kDeskImu) : 0;
     any = any || mode[j] != 0;
   }
-  if (any && !c->d_desk) CK(hipMalloc((void**)&c->d_desk, sizeof(fbr_deskew_table) * c->Bcap));
+  if (any && !c->d_desk && dalloc(c->d_desk, c->Bcap)) return FBR_ERR_HIP;
   CK(fbr_sync(c->stream));
   if (any) CK(fbr_memcpy_sync(c->d_desk, tables, sizeof(fbr_deskew_table) * n_tables, hipMemcpyHostToDevice));
   CK(fbr_memcpy_sync(c->d_desk_mode, mode.data(), sizeof(int32_t) * c->Bcap, hipMemcpyHostToDevice));
@@ -285,30 +285,37 @@ int fbr_batch_bytes(fbr_ctx* c, double* bytes_total, double* bytes_gn) {
 
 namespace {
 
-int ingest_init(fbr_ctx* c) {
-  Ingest& g = c->ing;
-  if (g.cstream) return FBR_OK;
+// Everything the ingest holds, or nothing: a set-up that fails part-way leaves `g` for the caller to
+// empty, so the next call starts over instead of finding a copy stream over missing buffers.
+// (static: this anonymous namespace stands inside extern "C", where the compiler exports its functions)
+static bool ingest_setup(fbr_ctx* c, Ingest& g) {
   const int64_t mb = knobs::stage_mb();
   g.chunk_bytes = std::max<int64_t>(mb << 20, c->NMAX * (int64_t)sizeof(fbr_point_xyzirt));
   g.chunk_bytes = (g.chunk_bytes + 63) & ~(int64_t)63;  // 16-B aligned records for the streaming stores
   // 16 packing threads (the CPU share of a one-GPU box; 8 -> 16: ingest line +10-20 %, r06m/r06n)
   g.nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
   if (const int t = knobs::stage_threads()) g.nthreads = t;
-  CK(hipStreamCreateWithFlags(&g.cstream, hipStreamNonBlocking));
-  if (knobs::ingest_xstream()) {
-    CK(hipStreamCreateWithFlags(&g.xstream, hipStreamNonBlocking));
-    CK(hipEventCreateWithFlags(&g.copied_ev, hipEventDisableTiming));
-  }
-  for (auto& e : g.up_ev) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  for (auto& e : g.chunk_ev) CK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  CK(hipHostMalloc((void**)&g.h_stage, (size_t)g.chunk_bytes * Ingest::kChunks, hipHostMallocDefault));
-  g.d_pts_slot[0] = c->d_pts;
-  if (dalloc(&g.d_pts_slot[1], (int64_t)c->Bcap * c->NMAX)) return FBR_ERR_HIP;
+  if (!g.cstream.create(hipStreamNonBlocking)) return false;
+  if (knobs::ingest_xstream() && !(g.xstream.create(hipStreamNonBlocking) && g.copied_ev.create(hipEventDisableTiming)))
+    return false;
+  for (auto& e : g.up_ev)
+    if (!e.create(hipEventDisableTiming)) return false;
+  for (auto& e : g.chunk_ev)
+    if (!e.create(hipEventDisableTiming)) return false;
+  if (dalloc(g.h_stage, (size_t)g.chunk_bytes * Ingest::kChunks) || dalloc(g.d_pts1, (int64_t)c->Bcap * c->NMAX))
+    return false;
+  g.d_pts_slot[0] = c->d_pts_own;
+  g.d_pts_slot[1] = g.d_pts1;
   for (int k = 0; k < (g.xstream ? 2 : 1); ++k)
-    if (dalloc(&g.d_stage[k], (int64_t)c->Bcap * ingest_region_bytes(c->NMAX))) return FBR_ERR_HIP;
-  if (dalloc(&g.d_nin, 4 * (int64_t)c->Bcap)) return FBR_ERR_HIP;
-  CK(hipHostMalloc((void**)&g.h_nin, sizeof(int64_t) * 4 * c->Bcap, hipHostMallocDefault));
-  return FBR_OK;
+    if (dalloc(g.d_stage[k], (int64_t)c->Bcap * ingest_region_bytes(c->NMAX))) return false;
+  return !dalloc(g.d_nin, 4 * (int64_t)c->Bcap) && !dalloc(g.h_nin, 4 * (int64_t)c->Bcap);
+}
+
+int ingest_init(fbr_ctx* c) {
+  if (c->ing.cstream) return FBR_OK;
+  if (ingest_setup(c, c->ing)) return FBR_OK;
+  c->ing = Ingest{};
+  return FBR_ERR_HIP;
 }
 
 // One scan's compact record (fbr_kernels.h: ingest_plane / ingest_region_bytes) at the 16-B aligned

@@ -43,14 +43,22 @@ const RcclApi& rccl() {
 }
 }  // namespace
 
-struct fbr_comm {
+struct __attribute__((visibility("hidden"))) fbr_comm {
   ncclComm_t nc = nullptr;
   int dev = 0, nranks = 0, rank = 0, max_jobs = 0;
-  float* send = nullptr;  // [max_jobs][8] this rank's padded records
-  hipEvent_t done = nullptr;  // after the latest all-gather: the next one (on another launch's
-  bool used = false;          // stream) reuses `send` and the caller's recv buffer
-  hipEvent_t ev_wait = nullptr;  // the caller's reader of recv (fbr_batch_allgather's wait_stream)
-  bool failed = false;        // a call returned an error: peers may be blocked, destroy aborts
+  Dev<float> send;        // [max_jobs][8] this rank's padded records
+  Event done;             // after the latest all-gather: the next one (on another launch's
+  bool used = false;      // stream) reuses `send` and the caller's recv buffer
+  Event ev_wait;          // the caller's reader of recv (fbr_batch_allgather's wait_stream)
+  bool failed = false;    // a call returned an error: peers may be blocked, destroy aborts
+
+  // Deleted on its own device, after `nc` has been ended (abort or destroy: fbr_comm_destroy,
+  // fbr_comm_create_local's cleanup); the handles then release themselves.
+  // this rank's send block and events; false on a failure (the caller deletes the communicator)
+  bool init(int max_jobs_per_rank) {
+    return dalloc(send, 8 * (size_t)max_jobs_per_rank) == FBR_OK && done.create(hipEventDisableTiming) &&
+           ev_wait.create(hipEventDisableTiming);
+  }
 };
 
 extern "C" {
@@ -80,19 +88,8 @@ int fbr_comm_create(fbr_comm** out, fbr_ctx* c, const uint8_t id[FBR_COMM_ID_BYT
   m->max_jobs = max_jobs_per_rank;
   ncclUniqueId uid;
   std::memcpy(uid.internal, id, FBR_COMM_ID_BYTES);
-  if (hipMalloc((void**)&m->send, sizeof(float) * 8 * (size_t)max_jobs_per_rank) != hipSuccess ||
-      hipEventCreateWithFlags(&m->done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&m->ev_wait, hipEventDisableTiming) != hipSuccess) {
-    (void)hipFree(m->send);
-    if (m->done) (void)hipEventDestroy(m->done);
-    delete m;
-    return FBR_ERR_HIP;
-  }
-  // blocks until every rank has joined (bootstrap over the id's socket)
-  if (rccl().comm_init_rank(&m->nc, nranks, uid, rank) != ncclSuccess) {
-    (void)hipFree(m->send);
-    (void)hipEventDestroy(m->done);
-    (void)hipEventDestroy(m->ev_wait);
+  // comm_init_rank blocks until every rank has joined (bootstrap over the id's socket)
+  if (!m->init(max_jobs_per_rank) || rccl().comm_init_rank(&m->nc, nranks, uid, rank) != ncclSuccess) {
     delete m;
     return FBR_ERR_HIP;
   }
@@ -118,9 +115,6 @@ int fbr_comm_create_local(fbr_comm** out, fbr_ctx* const* ctxs, int n, int max_j
       if (!q) continue;
       (void)hipSetDevice(q->dev);
       if (q->nc) (void)rccl().comm_abort(q->nc);
-      (void)hipFree(q->send);
-      if (q->done) (void)hipEventDestroy(q->done);
-      if (q->ev_wait) (void)hipEventDestroy(q->ev_wait);
       delete q;
     }
   };
@@ -134,9 +128,7 @@ int fbr_comm_create_local(fbr_comm** out, fbr_ctx* const* ctxs, int n, int max_j
     m[i]->nranks = n;
     m[i]->rank = i;
     m[i]->max_jobs = max_jobs_per_rank;
-    if (hipMalloc((void**)&m[i]->send, sizeof(float) * 8 * (size_t)max_jobs_per_rank) != hipSuccess ||
-        hipEventCreateWithFlags(&m[i]->done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&m[i]->ev_wait, hipEventDisableTiming) != hipSuccess) {
+    if (!m[i]->init(max_jobs_per_rank)) {
       cleanup();
       return FBR_ERR_HIP;
     }
@@ -163,9 +155,6 @@ int fbr_comm_destroy(fbr_comm* m) {
   // after a failed collective the peers may be inside an all-gather this rank never joined:
   // abort (tear down without the collective handshake) instead of destroying
   if (m->nc && (m->failed ? rccl().comm_abort(m->nc) : rccl().comm_destroy(m->nc)) != ncclSuccess) rc = FBR_ERR_HIP;
-  (void)hipFree(m->send);
-  if (m->done) (void)hipEventDestroy(m->done);
-  if (m->ev_wait) (void)hipEventDestroy(m->ev_wait);
   delete m;
   return rc;
 }

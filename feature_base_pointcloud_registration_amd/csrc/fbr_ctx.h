@@ -1,7 +1,7 @@
 // fbr_ctx.h — internal to the host units (fbr_*.hip): the context behind include/fbr.h's opaque
 // fbr_ctx, the small helpers every unit uses, and the few functions that cross units.
 //
-//   fbr_api.hip     life cycle (the one allocation list and its frees), profiling timers, diagnostics
+//   fbr_api.hip     life cycle (fbr_create's allocations, the drain before ~fbr_ctx), profiling timers, diagnostics
 //   fbr_stages.hip  per-stage launch glue, the Gauss-Newton run driver and its flag waits, results
 //   fbr_scan.hip    single-scan entry points, their upload path and copy-worker pool
 //   fbr_batch.hip   batch stage / launch / export state machine, the pinned-ring ingest
@@ -36,6 +36,7 @@
 #include "fbr_kernels.h"
 #include "fbr_knobs.h"
 #include "fbr_msg.h"
+#include "fbr_own.h"
 
 using namespace fbr;
 
@@ -67,32 +68,99 @@ inline hipError_t fbr_memcpy_sync(void* dst, const void* src, size_t bytes, hipM
   return hipMemcpy(dst, src, bytes, kind);
 }
 
+// ---- the HIP policies of fbr_own.h's handles; they keep the live-resource counts ----
+inline bool hip_ok(hipError_t e, const char* what) {
+  if (e != hipSuccess) fprintf(stderr, "fbr: HIP error %s in %s\n", hipGetErrorString(e), what);
+  return e == hipSuccess;
+}
+struct DeviceMem {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+    own::live_add(own::kLiveDevice, 1);
+    return p;
+  }
+  static void release(void* p) {
+    (void)hipFree(p);
+    own::live_add(own::kLiveDevice, -1);
+  }
+};
+template <unsigned Flags>  // hipHostMallocDefault or hipHostMallocMapped
+struct PinnedMem {
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, bytes, Flags) != hipSuccess) return nullptr;
+    own::live_add(own::kLivePinned, 1);
+    return p;
+  }
+  static void release(void* p) {
+    (void)hipHostFree(p);
+    own::live_add(own::kLivePinned, -1);
+  }
+};
+struct StreamPolicy {
+  static bool create(hipStream_t* s, unsigned flags) {
+    if (!hip_ok(hipStreamCreateWithFlags(s, flags), "hipStreamCreateWithFlags")) return false;
+    own::live_add(own::kLiveStream, 1);
+    return true;
+  }
+  static void release(hipStream_t s) {
+    (void)hipStreamDestroy(s);
+    own::live_add(own::kLiveStream, -1);
+  }
+};
+struct EventPolicy {
+  static bool create(hipEvent_t* e, unsigned flags) {
+    if (!hip_ok(hipEventCreateWithFlags(e, flags), "hipEventCreateWithFlags")) return false;
+    own::live_add(own::kLiveEvent, 1);
+    return true;
+  }
+  static void release(hipEvent_t e) {
+    (void)hipEventDestroy(e);
+    own::live_add(own::kLiveEvent, -1);
+  }
+};
 template <typename T>
-int dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  CK(hipMalloc((void**)p, sizeof(T) * count));
-  return FBR_OK;
+using Dev = own::Owned<T, DeviceMem>;
+template <typename T>
+using GrowDev = own::Growable<T, DeviceMem>;
+template <typename T>
+using Pinned = own::Owned<T, PinnedMem<hipHostMallocDefault>>;
+template <typename T>
+using GrowPinned = own::Growable<T, PinnedMem<hipHostMallocDefault>>;
+template <typename T>
+using Mapped = own::Owned<T, PinnedMem<hipHostMallocMapped>>;  // host-mapped: the device writes it
+using Stream = own::Unique<hipStream_t, StreamPolicy>;
+using Event = own::Unique<hipEvent_t, EventPolicy>;
+
+// A handle's alloc() failed where that is an error (the memory policies themselves are quiet: a
+// caller with a fallback stays silent): report the runtime's error.
+inline int alloc_failed() {
+  (void)hip_ok(hipPeekAtLastError(), "an allocation");
+  return FBR_ERR_HIP;
 }
 
-// Grow a device array to hold `need` elements (keeping `keep` of them).
-template <typename T>
-int grow(T** p, int64_t* cap, int64_t need, int64_t keep, hipStream_t st) {
-  if (need <= *cap) return FBR_OK;
-  const int64_t ncap = std::max<int64_t>(need, *cap * 2 + 1024);
-  T* q = nullptr;
-  CK(hipMalloc((void**)&q, sizeof(T) * ncap));
-  if (*p && keep > 0) CK(hipMemcpyAsync(q, *p, sizeof(T) * keep, hipMemcpyDeviceToDevice, st));
-  CK(fbr_sync(st));
-  if (*p) CK(hipFree(*p));
-  *p = q;
-  *cap = ncap;
-  return FBR_OK;
+// `count` elements (at least one) of device or pinned memory, by the handle's type.
+template <typename T, typename Mem>
+int dalloc(own::Owned<T, Mem>& p, size_t count) {
+  return p.alloc(count) ? FBR_OK : alloc_failed();
 }
 
+// Grow a device array to hold `need` elements (keeping `keep` of them): own::Growable's rule, with
+// the copy on `st` and its sync as the step the old block has to outlive.
+template <typename T>
+int grow(GrowDev<T>& g, int64_t need, int64_t keep, hipStream_t st) {
+  const bool ok = g.grow(need, keep, [st](T* dst, const T* src, int64_t n) {
+    if (n > 0 && !hip_ok(hipMemcpyAsync(dst, src, sizeof(T) * n, hipMemcpyDeviceToDevice, st), "grow")) return false;
+    return hip_ok(fbr_sync(st), "grow");
+  });
+  return ok ? FBR_OK : FBR_ERR_HIP;
+}
+
+// Timed launches' event pairs (timing enabled), reused through the pool.
 struct KernelTimer {
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+  std::vector<std::pair<Event, Event>> pending;
+  std::vector<std::pair<Event, Event>> pool;
   double total_ms = 0.0;
   int64_t launches = 0;
 };
@@ -107,29 +175,32 @@ constexpr int kMaxSub = 8;  // sub-batch streams per launch (FBR_NSUB); more tha
 // Host ingest of fbr_process_batch: the caller's (pageable) scans are packed into a ring of pinned
 // staging chunks by host threads and copied to HBM on a copy stream, into the input slot the
 // running device batch does not read; batch k+1's upload overlaps batch k's compute.
-struct Ingest {
+// Empty (no copy stream) until ingest_init has set all of it up; streams and events stand before
+// the buffers, so they are destroyed after them.
+struct __attribute__((visibility("hidden"))) Ingest {
   static constexpr int kChunks = 4;
-  hipStream_t cstream = nullptr;
-  hipStream_t xstream = nullptr;     // k_expand_scans, off the copy stream (FBR_INGEST_XSTREAM=0: on it)
-  hipEvent_t copied_ev = nullptr;    // the copies of the current upload are done (on cstream)
-  hipEvent_t up_ev[2] = {};          // the upload of input slot s is complete (on xstream / cstream)
-  hipEvent_t chunk_ev[kChunks] = {};  // the copies out of chunk k are complete
+  Stream cstream;
+  Stream xstream;                    // k_expand_scans, off the copy stream (FBR_INGEST_XSTREAM=0: on it)
+  Event copied_ev;                   // the copies of the current upload are done (on cstream)
+  Event up_ev[2];                    // the upload of input slot s is complete (on xstream / cstream)
+  Event chunk_ev[kChunks];           // the copies out of chunk k are complete
   bool chunk_used[kChunks] = {};
   int next_chunk = 0;
-  uint8_t* h_stage = nullptr;        // kChunks x chunk_bytes, pinned
+  Pinned<uint8_t> h_stage;           // kChunks x chunk_bytes
   int64_t chunk_bytes = 0;
-  fbr_point_xyzirt* d_pts_slot[2] = {};  // slot 0 = the context's scan buffer, slot 1 allocated here
+  Dev<fbr_point_xyzirt> d_pts1;          // input slot 1's scan buffer
+  fbr_point_xyzirt* d_pts_slot[2] = {};  // not owning: slot 0 = the context's d_pts_own, slot 1 = d_pts1
   int nthreads = 8;                  // packing threads per chunk
   double h2d_bytes = 0.0;            // bytes copied host -> device by the last fbr_process_batch
   // Compact records (no deskew tables set: `time` is never read): per scan the x, y, z planes
   // (f32) and the rings (u8 below 256 rings), 13 B per point instead of 24, expanded on the device
   // by k_expand_scans (the batch returns poses and statistics, which no point's intensity or time
   // reaches).
-  uint8_t* d_stage[2] = {};          // per input slot: [Bcap][ingest_region_bytes(NMAX)] (one per
+  Dev<uint8_t> d_stage[2];           // per input slot: [Bcap][ingest_region_bytes(NMAX)] (one per
                                      // slot, so slot s's expand overlaps slot s^1's copies)
-  int64_t* d_nin = nullptr;          // [2][2][Bcap] per input slot: the staged scans' point counts,
+  Dev<int64_t> d_nin;                // [2][2][Bcap] per input slot: the staged scans' point counts,
                                      // then their records' byte offsets in d_stage (copy stream)
-  int64_t* h_nin = nullptr;          // [2][2][Bcap] pinned
+  Pinned<int64_t> h_nin;             // [2][2][Bcap]
   bool compact_used = false;         // the last fbr_process_batch used compact records
   bool pk_slot[2] = {};              // input slot s holds 16-B device records (launch_expand_scans pk)
 };
@@ -186,9 +257,14 @@ struct WaitBound {
 enum { kWaitBatchFlag = 0, kWaitScanFlag = 1, kWaitDirect = 2 };
 
 // Members stand under the unit that owns them: the unit that gives them their meaning and, but for
-// the allocation list, writes them.  fbr_create / fbr_destroy (fbr_api.hip) allocate and free every
-// array that is not "grown on demand" or "allocated on first use".
-struct fbr_ctx {
+// fbr_create's allocations, writes them.
+//
+// Ownership: every array, stream and event is an owning handle (fbr_own.h) and is released by
+// ~fbr_ctx, whichever unit allocated it and whenever ("grown on demand", "allocated on first
+// use"); a raw pointer member does not own and says so.  Members are destroyed in reverse order of
+// declaration: the streams, the events, the ingest and the timers stand first, so they go after
+// every buffer.  fbr_destroy drains the streams before it deletes the context.
+struct __attribute__((visibility("hidden"))) fbr_ctx {
   fbr_params P;
   int dev = 0;
   int H = 0, W = 0, Bcap = 0;
@@ -196,72 +272,82 @@ struct fbr_ctx {
   int items_per_job = 0;
   int max_items = 0;
 
+  ~fbr_ctx() {
+    free_grid(grid_c);
+    free_grid(grid_s);
+    free_grid(icp_grid);
+    arena_free(arena);
+  }
+
   // ---- streams and events (fbr_api.hip creates them; every unit enqueues on them) ----
-  hipStream_t stream = nullptr;   // primary stream (single-scan calls, batch sub-batch 0, export)
-  hipStream_t xstream[kMaxSub] = {};  // extra streams of batch sub-batches 1.. (index 0 unused)
-  hipEvent_t xev[kMaxSub] = {};       // fork / join events
-  hipEvent_t ev_staged = nullptr;  // the staged inputs are on the device (recorded on stream)
-  hipEvent_t ev_fork = nullptr;    // single-scan side-stream fork
-  hipEvent_t ev_ext = nullptr;     // a caller's stream, waited on before an export (fbr_batch_export_ready)
-  DevArena arena;                      // scratch of the set-up paths (map VoxelGrid, grid builds)
+  Stream stream;            // primary stream (single-scan calls, batch sub-batch 0, export)
+  Stream xstream[kMaxSub];  // extra streams of batch sub-batches 1.. (index 0 unused)
+  Event xev[kMaxSub];       // fork / join events
+  Event ev_staged;          // the staged inputs are on the device (recorded on stream)
+  Event ev_fork;            // single-scan side-stream fork
+  Event ev_ext;             // a caller's stream, waited on before an export (fbr_batch_export_ready)
+  Ingest ing;               // fbr_process_batch host ingest (fbr_batch.hip; allocated on first use)
+  std::map<std::string, KernelTimer> timers;  // profiling (fbr_api.hip)
+  DevArena arena;           // scratch of the set-up paths (map VoxelGrid, grid builds)
 
   // ---- stage inputs and work arrays: projection, features, mapping DS (fbr_stages.hip) ----
   // inputs
-  fbr_point_xyzirt* d_pts = nullptr;
-  int64_t* d_nin = nullptr;
-  float* d_guess = nullptr;
+  Dev<fbr_point_xyzirt> d_pts_own;    // [Bcap][NMAX] the context's scan buffer
+  fbr_point_xyzirt* d_pts = nullptr;  // not owning: the scan buffer the stages read, d_pts_own but
+                                      // for the ingest slot of a running fbr_process_batch
+  Dev<int64_t> d_nin;
+  Dev<float> d_guess;
   // projection
   // owner image generations (OwnerTag, fbr_kernels.h): owner_ib index bits, owner_tmax the last
   // generation before the image is refilled (0: untagged, reset by k_compact)
   int owner_ib = 0;
   uint32_t owner_gen = 0, owner_tmax = 0;
-  int32_t *d_owner = nullptr, *d_rowcnt = nullptr, *d_col = nullptr, *d_start = nullptr, *d_end = nullptr,
-          *d_nvalid = nullptr;
-  float4* d_cloud = nullptr;
-  float* d_range = nullptr;
+  Dev<int32_t> d_owner, d_rowcnt, d_col, d_start, d_end, d_nvalid;
+  Dev<float4> d_cloud;
+  Dev<float> d_range;
   // features
-  StreamState* d_sstate = nullptr;    // [Bcap] batch (zeroed per batch)
-  StreamState* d_sstream = nullptr;   // [1]   stream mode (persistent)
-  int8_t* d_label = nullptr;          // [Bcap][HW]
-  int8_t* d_label_stream = nullptr;   // [HW]   stream mode (persistent)
-  float4* d_corner_slot = nullptr;
-  int32_t* d_corner_cnt = nullptr;
-  float4* d_surf_ring = nullptr;
-  int32_t* d_surf_ring_cnt = nullptr;
-  float* d_ring_box = nullptr;  // [B][H][kRingBox]: k_concat's per-ring cloud bounds
+  Dev<StreamState> d_sstate;     // [Bcap] batch (zeroed per batch)
+  Dev<StreamState> d_sstream;    // [1]   stream mode (persistent)
+  Dev<int8_t> d_label;           // [Bcap][HW]
+  Dev<int8_t> d_label_stream;    // [HW]   stream mode (persistent)
+  Dev<float4> d_corner_slot;
+  Dev<int32_t> d_corner_cnt;
+  Dev<float4> d_surf_ring;
+  Dev<int32_t> d_surf_ring_cnt;
+  Dev<float> d_ring_box;        // [B][H][kRingBox]: k_concat's per-ring cloud bounds
   bool ring_box_valid = false;  // d_corner_all / d_surf_all came from k_concat (not upload_cloud)
-  int32_t* d_err = nullptr;
-  float4 *d_corner_all = nullptr, *d_surf_all = nullptr, *d_cornerDS = nullptr, *d_surfDS = nullptr;
-  int32_t *d_ncorner = nullptr, *d_nsurf = nullptr, *d_ncds = nullptr, *d_nsds = nullptr;
-  uint32_t* d_vg_scratch = nullptr;
+  Dev<int32_t> d_err;
+  Dev<float4> d_corner_all, d_surf_all, d_cornerDS, d_surfDS;
+  Dev<int32_t> d_ncorner, d_nsurf, d_ncds, d_nsds;
+  Dev<uint32_t> d_vg_scratch;
   int64_t vg_scratch_elems = 0;
-  unsigned char* d_feat_scratch = nullptr;  // k_features sorted-path slots [B*H][gslot_bytes]
+  Dev<unsigned char> d_feat_scratch;  // k_features sorted-path slots [B*H][gslot_bytes]
   // IMU deskew (fbr_set_deskew, fbr_batch.hip, fills the tables)
-  fbr_deskew_table* d_desk = nullptr;  // [Bcap] tables (allocated on first use)
-  int32_t* d_desk_mode = nullptr;      // [Bcap] kDesk* bits per job
-  int32_t* d_rowmin = nullptr;         // [Bcap][H] minimum owner per row
-  int32_t* d_choff = nullptr;          // [Bcap][H][W / 32 + 1] compaction tile offsets
-  bool desk_any = false;               // some job has a non-zero mode
-  bool no_time_call = false;           // the current call's PointCloud2 has no "time" field
+  Dev<fbr_deskew_table> d_desk;  // [Bcap] tables (allocated on first use)
+  Dev<int32_t> d_desk_mode;      // [Bcap] kDesk* bits per job
+  Dev<int32_t> d_rowmin;         // [Bcap][H] minimum owner per row
+  Dev<int32_t> d_choff;          // [Bcap][H][W / 32 + 1] compaction tile offsets
+  bool desk_any = false;         // some job has a non-zero mode
+  bool no_time_call = false;     // the current call's PointCloud2 has no "time" field
 
   // ---- Gauss-Newton work arrays, run driver state and results (fbr_stages.hip) ----
-  GnState* d_gn = nullptr;
-  int4* d_items = nullptr;
-  int32_t *d_nitems = nullptr, *d_item_range = nullptr, *d_cropcnt = nullptr;
-  int32_t* d_cropwork = nullptr;  // [Bwork][2]: a launch's CropBox counts while they accumulate
-  double* d_partial = nullptr;
-  int32_t* d_nbr = nullptr;
-  float* d_fitc = nullptr;     // [max_items][6][256] per-query fit cache (k_gn_residual)
-  int8_t* d_fits = nullptr;    // [max_items][256]
-  int8_t* d_nsame = nullptr;   // [max_items][256]
+  Dev<GnState> d_gn;
+  Dev<int4> d_items;
+  Dev<int32_t> d_nitems, d_item_range, d_cropcnt;
+  Dev<int32_t> d_cropwork;  // [Bwork][2]: a launch's CropBox counts while they accumulate
+  Dev<double> d_partial;
+  Dev<int32_t> d_nbr;
+  Dev<float> d_fitc;     // [max_items][6][256] per-query fit cache (k_gn_residual)
+  Dev<int8_t> d_fits;    // [max_items][256]
+  Dev<int8_t> d_nsame;   // [max_items][256]
   // block-tile kNN (k_knn_tile.hip), allocated by build_map_grids when the map's grids take it:
-  int32_t* d_fb_list = nullptr;  // [3][max_items][256] queued / binned query slots, query blocks
-  int32_t* d_bin = nullptr;      // [kMaxSub][3][bin_nb] per-block counts, cursors, non-empty list
+  Dev<int32_t> d_fb_list;  // [3][max_items][256] queued / binned query slots, query blocks
+  Dev<int32_t> d_bin;      // [kMaxSub][3][bin_nb] per-block counts, cursors, non-empty list
   int64_t bin_nb = 0, bin_nb_c = 0;
-  unsigned long long* h_iter_flags = nullptr;  // host-mapped, written by k_gn_solve
-  unsigned long long* d_iter_flags = nullptr;  // its device address
+  Mapped<unsigned long long> h_iter_flags;     // host-mapped, written by k_gn_solve
+  unsigned long long* d_iter_flags = nullptr;  // not owning: h_iter_flags' device address
   unsigned long long gn_gen = 0;
-  int32_t* d_iter_cnt = nullptr;
+  Dev<int32_t> d_iter_cnt;
   WaitBound wait_bound[3];            // kWaitBatchFlag / kWaitScanFlag / kWaitDirect
   int gn_items_hint = 0, gn_items_hint_B = 0;  // the last batch run's work items and its job count
   // Work items of the previous single scan: the next one's Gauss-Newton grids are sized from it
@@ -270,11 +356,11 @@ struct fbr_ctx {
   // ~870 workgroups (x 8 in the wide kNN mode) that found no item.
   int items_hint = 0;
   bool crop_cached = false;  // d_cropcnt holds the staged batch's CropBox statistics
-  float* d_pose_out = nullptr;
-  fbr_reg_stats* d_stats = nullptr;
-  float* d_trace = nullptr;
-  JobResult* d_result = nullptr;          // [Bcap] packed per-job results
-  JobResult* h_result = nullptr;          // [Bcap] pinned
+  Dev<float> d_pose_out;
+  Dev<fbr_reg_stats> d_stats;
+  Dev<float> d_trace;
+  Dev<JobResult> d_result;     // [Bcap] packed per-job results
+  Pinned<JobResult> h_result;  // [Bcap]
   std::vector<int32_t> last_iters, last_q, last_n, last_m;
 
   // ---- single-scan state (fbr_scan.hip) ----
@@ -283,23 +369,21 @@ struct fbr_ctx {
   double time_last = -1.0;
   int stream_degenerate = 0;  // mapOptimization::isDegenerate across single-scan registrations
   bool crop_join = false;    // single scan: copy_results takes the CropBox counts from h_crop (side stream)
-  int32_t* h_crop = nullptr;  // pinned [2]: the single-scan CropBox counts
-  float* h_guess = nullptr;   // pinned [6]: the single-scan guess (queue_guess)
-  fbr_point_xyzirt* h_scan = nullptr;     // [NMAX] pinned staging of single-scan uploads
-  int64_t* h_nin = nullptr;               // pinned scalar
-  uint8_t* d_msg = nullptr;                 // raw PointCloud2 bytes of the last *_msg call (grown on demand)
-  uint64_t msg_cap = 0;
-  uint8_t* h_msg = nullptr;               // pinned staging of raw PointCloud2 bytes (grown on demand)
-  uint64_t h_msg_cap = 0;
+  Pinned<int32_t> h_crop;          // [2]: the single-scan CropBox counts
+  Pinned<float> h_guess;           // [6]: the single-scan guess (queue_guess)
+  Pinned<fbr_point_xyzirt> h_scan;  // [NMAX] staging of single-scan uploads
+  Pinned<int64_t> h_nin;           // scalar
+  GrowDev<uint8_t> d_msg;          // raw PointCloud2 bytes of the last *_msg call (grown on demand)
+  GrowPinned<uint8_t> h_msg;       // staging of raw PointCloud2 bytes (grown on demand)
   // fbr_process_scan's direct result (GnArgs::direct): the ending k_gn_solve packs the job's
   // result into h_direct (host-mapped); the host spins on its generation word instead of
   // enqueueing finalize + pack + copy and synchronising.  The no-op iterations the host had
   // enqueued ahead of the last flag may still be queued when the call returns (tail_pending):
   // the next single-scan call is ordered after them on the stream, every other entry point
   // synchronises the stream first (enter).
-  JobResult* h_direct = nullptr;
-  JobResult* d_direct = nullptr;
-  int32_t* d_direct_done = nullptr;
+  Mapped<JobResult> h_direct;
+  JobResult* d_direct = nullptr;  // not owning: h_direct's device address
+  Dev<int32_t> d_direct_done;
   int32_t direct_gen = 0;     // generation of the current single-scan run (0: direct off)
   int32_t direct_gen_seq = 0;
   bool tail_pending = false;
@@ -325,12 +409,9 @@ struct fbr_ctx {
   std::vector<int64_t> staged_nin;
   // the staged batch's 16-B device records (fbr_kernels.h: x, y, z, ring bits), null = the 24-B
   // scans in d_pts; d_pk backs them for fbr_batch_stage (fbr_process_batch expands into its slots)
-  float4* d_pk = nullptr;
-  const float4* staged_pk = nullptr;
+  Dev<float4> d_pk;
+  const float4* staged_pk = nullptr;  // not owning: d_pk or an ingest slot's records
   bool staged_24 = false;  // d_pts holds the staged batch's 24-B scans (a deskewing launch needs them)
-
-  // ---- ingest of fbr_process_batch (fbr_batch.hip) ----
-  Ingest ing;                 // fbr_process_batch host ingest (allocated on first use)
 
   // ---- map grids (fbr_map.hip) ----
   bool has_map = false;
@@ -342,42 +423,35 @@ struct fbr_ctx {
   // LIO-SAM keyframe store (fbr_keyframes_*) and the local map built from it
   std::vector<fbr_keypose> kf_poses;
   std::vector<int64_t> kf_c_off, kf_c_cnt, kf_s_off, kf_s_cnt;
-  float4 *d_kf_c = nullptr, *d_kf_s = nullptr;  // lidar-frame keyframe clouds, appended
-  int64_t kf_c_cap = 0, kf_s_cap = 0, kf_c_used = 0, kf_s_used = 0;
-  float4 *d_kraw_c = nullptr, *d_kraw_s = nullptr;  // concatenated transformed clouds
-  int64_t kraw_c_cap = 0, kraw_s_cap = 0;
-  float4 *d_kds_c = nullptr, *d_kds_s = nullptr;    // their VoxelGrids (laserCloud*FromMapDS)
+  GrowDev<float4> d_kf_c, d_kf_s;  // lidar-frame keyframe clouds, appended
+  int64_t kf_c_used = 0, kf_s_used = 0;
+  GrowDev<float4> d_kraw_c, d_kraw_s;  // concatenated transformed clouds
+  Dev<float4> d_kds_c, d_kds_s;        // their VoxelGrids (laserCloud*FromMapDS)
   int64_t kds_c_n = 0, kds_s_n = 0;
-  KfSeg* d_kf_segs = nullptr;
-  int64_t kf_segs_cap = 0;
-  int* d_bounds = nullptr;
+  GrowDev<KfSeg> d_kf_segs;
 
   // ---- loop closure / ICP scratch (fbr_loop.hip) ----
   // loop closure ICP (fbr_perform_loop_closure, fbr_icp_align): scratch of its own, grown on demand
-  float4 *d_icp_src = nullptr, *d_icp_x = nullptr, *d_icp_raw = nullptr, *d_icp_tgt = nullptr;
-  int64_t icp_src_cap = 0, icp_x_cap = 0, icp_raw_cap = 0, icp_tgt_cap = 0;
-  unsigned long long* d_icp_key = nullptr;
-  int32_t* d_icp_far = nullptr;       // [n + 1]: the far-query list, then its count
-  double* d_icp_partial = nullptr;
-  int64_t icp_key_cap = 0, icp_far_cap = 0, icp_partial_cap = 0;
-  KfSeg* d_icp_segs = nullptr;
-  int64_t icp_segs_cap = 0;
-  IcpState* d_icp_state = nullptr;    // the state, then the fbr_icp_result record
-  unsigned long long* h_icp_flag = nullptr;  // host-mapped stop word, written by k_icp_solve
-  unsigned long long* d_icp_flag = nullptr;
+  GrowDev<float4> d_icp_src, d_icp_x, d_icp_raw, d_icp_tgt;
+  GrowDev<unsigned long long> d_icp_key;
+  GrowDev<int32_t> d_icp_far;  // [n + 1]: the far-query list, then its count
+  GrowDev<double> d_icp_partial;
+  GrowDev<KfSeg> d_icp_segs;
+  Dev<IcpState> d_icp_state;   // the state, then the fbr_icp_result record
+  Mapped<unsigned long long> h_icp_flag;     // host-mapped stop word, written by k_icp_solve
+  unsigned long long* d_icp_flag = nullptr;  // not owning: h_icp_flag's device address
   unsigned long long icp_gen = 0;
-  DevGrid icp_grid;                   // the ICP's own grid over its target
+  DevGrid icp_grid;            // the ICP's own grid over its target
 
-  // ---- profiling (fbr_api.hip) ----
+  // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;
-  std::map<std::string, KernelTimer> timers;
   std::set<std::string> profile_only;  // empty: time every kernel
 
   // ---- diagnostics (fbr_api.hip) ----
   int diag_err_job = -1;      // diagnostic (fbr_diag_force_capacity_error): batch job flagged over capacity
   int diag_ring_filter = -1;  // diagnostic (fbr_diag_ring_filter): per-ring surf filter kernel, -1 = by size
-  unsigned long long* d_feat_stamps = nullptr;  // diagnostic builds (FBR_FEAT_STAMPS) only
-  uint32_t* d_feat_paths = nullptr;             // tests (fbr_diag_feature_paths): FeatArgs::paths [Bwork][H]
+  Dev<unsigned long long> d_feat_stamps;  // diagnostic builds (FBR_FEAT_STAMPS) only
+  Dev<uint32_t> d_feat_paths;             // tests (fbr_diag_feature_paths): FeatArgs::paths [Bwork][H]
 };
 
 namespace fbr {

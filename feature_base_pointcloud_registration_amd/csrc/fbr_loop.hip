@@ -43,14 +43,14 @@ bool loop_candidate(const fbr_ctx* c, double stamp, const fbr_loop_params* lp, i
 int icp_prepare(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt, int64_t nt, float cell_hint, IcpArgs* a) {
   if (ns >= ((int64_t)1 << 30) || nt >= ((int64_t)1 << 28)) return FBR_ERR_CAPACITY;
   const int64_t nblk = (ns + 255) / 256;
-  int rc = grow(&c->d_icp_x, &c->icp_x_cap, std::max<int64_t>(ns, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_key, &c->icp_key_cap, std::max<int64_t>(ns, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_far, &c->icp_far_cap, ns + 1, 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_partial, &c->icp_partial_cap, std::max<int64_t>(nblk, 1) * kIcpSums, 0, c->stream);
+  int rc = grow(c->d_icp_x, std::max<int64_t>(ns, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_key, std::max<int64_t>(ns, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_far, ns + 1, 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_partial, std::max<int64_t>(nblk, 1) * kIcpSums, 0, c->stream);
   if (rc) return rc;
-  if (!c->d_icp_state) CK(hipMalloc((void**)&c->d_icp_state, sizeof(IcpState) + sizeof(fbr_icp_result)));
+  if (!c->d_icp_state && !c->d_icp_state.alloc_bytes(sizeof(IcpState) + sizeof(fbr_icp_result))) return alloc_failed();
   if (!c->h_icp_flag) {
-    CK(hipHostMalloc((void**)&c->h_icp_flag, sizeof(unsigned long long), hipHostMallocMapped));
+    if (dalloc(c->h_icp_flag, 1)) return FBR_ERR_HIP;
     *c->h_icp_flag = 0;
     CK(hipHostGetDevicePointer((void**)&c->d_icp_flag, c->h_icp_flag, 0));
   }
@@ -135,10 +135,10 @@ int icp_run(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt, in
   return FBR_OK;
 }
 
-int icp_upload(fbr_ctx* c, float4** dst, int64_t* cap, const fbr_point_xyzi* src, int64_t n) {
-  const int rc = grow(dst, cap, std::max<int64_t>(n, 1), 0, c->stream);
+int icp_upload(fbr_ctx* c, GrowDev<float4>& dst, const fbr_point_xyzi* src, int64_t n) {
+  const int rc = grow(dst, std::max<int64_t>(n, 1), 0, c->stream);
   if (rc) return rc;
-  if (n) CK(hipMemcpyAsync(*dst, src, sizeof(float4) * n, hipMemcpyHostToDevice, c->stream));
+  if (n) CK(hipMemcpyAsync(dst, src, sizeof(float4) * n, hipMemcpyHostToDevice, c->stream));
   CK(fbr_sync(c->stream));
   return FBR_OK;
 }
@@ -224,10 +224,10 @@ int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp
   const int nseg = (int)cseg.size();  // 1 source segment + the target's, per pool
   std::vector<KfSeg> segs(cseg);
   segs.insert(segs.end(), sseg.begin(), sseg.end());
-  int rc = grow(&c->d_icp_src, &c->icp_src_cap, std::max<int64_t>(n_src, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_raw, &c->icp_raw_cap, std::max<int64_t>(n_raw, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_tgt, &c->icp_tgt_cap, std::max<int64_t>(n_raw, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_icp_segs, &c->icp_segs_cap, (int64_t)segs.size(), 0, c->stream);
+  int rc = grow(c->d_icp_src, std::max<int64_t>(n_src, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_raw, std::max<int64_t>(n_raw, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_tgt, std::max<int64_t>(n_raw, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_icp_segs, (int64_t)segs.size(), 0, c->stream);
   if (rc) return rc;
   CK(hipMemcpyAsync(c->d_icp_segs, segs.data(), sizeof(KfSeg) * segs.size(), hipMemcpyHostToDevice, c->stream));
   launch_kf_transform(c->stream, c->d_kf_c, c->d_icp_segs, 1, max_cnt, c->d_icp_src);
@@ -289,8 +289,8 @@ int fbr_icp_align(fbr_ctx* c, const fbr_point_xyzi* source, int64_t n_source, co
     return FBR_ERR_INVALID_ARG;
   CK(enter(c));
   std::memset(out, 0, sizeof(*out));
-  int rc = icp_upload(c, &c->d_icp_src, &c->icp_src_cap, source, n_source);
-  if (!rc) rc = icp_upload(c, &c->d_icp_tgt, &c->icp_tgt_cap, target, n_target);
+  int rc = icp_upload(c, c->d_icp_src, source, n_source);
+  if (!rc) rc = icp_upload(c, c->d_icp_tgt, target, n_target);
   if (rc) return rc;
   return icp_run(c, c->d_icp_src, n_source, c->d_icp_tgt, n_target, *ip, c->P.mapping_surf_leaf_size, out);
 }
@@ -301,8 +301,8 @@ int fbr_selftest_nn1(fbr_ctx* c, const fbr_point_xyzi* target, int64_t n_target,
       !(max_distance >= 0.0f))
     return FBR_ERR_INVALID_ARG;
   CK(enter(c));
-  int rc = icp_upload(c, &c->d_icp_src, &c->icp_src_cap, query, n_query);
-  if (!rc) rc = icp_upload(c, &c->d_icp_tgt, &c->icp_tgt_cap, target, n_target);
+  int rc = icp_upload(c, c->d_icp_src, query, n_query);
+  if (!rc) rc = icp_upload(c, c->d_icp_tgt, target, n_target);
   IcpArgs a;
   if (!rc) rc = icp_prepare(c, c->d_icp_src, n_query, c->d_icp_tgt, n_target, c->P.mapping_surf_leaf_size, &a);
   if (rc) return rc;

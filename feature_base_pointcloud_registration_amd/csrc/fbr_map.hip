@@ -18,7 +18,8 @@ void grid_cell_sizes(const fbr_params& P, float* inv_yz, float* inv_x) {
   *inv_x = knobs::knn_cell_x_inv(sparse);
 }
 
-// One-segment device VoxelGrid with temporary buffers (map start-up filter, fbr_voxel_grid).
+// One-segment device VoxelGrid of a host cloud (map start-up filter, fbr_voxel_grid): upload,
+// voxel_grid_dev, download.
 int voxel_grid_once(fbr_ctx* c, const fbr_point_xyzi* in, int64_t n, float leaf, std::vector<fbr_point_xyzi>& out) {
   out.clear();
   if (n <= 0) return FBR_OK;
@@ -33,64 +34,15 @@ int voxel_grid_once(fbr_ctx* c, const fbr_point_xyzi* in, int64_t n, float leaf,
       return voxel_grid_once(c, fin.data(), (int64_t)fin.size(), leaf, out);
     }
   if (n > INT32_MAX / 4) return FBR_ERR_CAPACITY;
-  float4 *d_in = nullptr, *d_out = nullptr;
-  int32_t* d_cnt = nullptr;
-  uint32_t* d_sc = nullptr;
-  int rc = FBR_OK;
-  const bool large = n >= knobs::vg_large_min();
-  // d_cnt: {input count, output count, look-back error word (k_voxel_grid_split: a part that gave
-  // up its look-back flags it, whichever part writes the count)}
-  if (dalloc(&d_in, n) || dalloc(&d_out, n) || dalloc(&d_cnt, 3) || (!large && dalloc(&d_sc, kVgScratch * n))) {
-    rc = FBR_ERR_HIP;
-  } else {
-    int32_t nn = (int32_t)n;
-    if (hipMemcpyAsync(d_in, in, sizeof(float4) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(d_cnt, &nn, sizeof(int32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess) {
-      rc = FBR_ERR_HIP;
-    } else if (large) {
-      rc = voxel_grid_large(c->stream, c->arena, d_in, n, leaf, 0, c->P.exact_voxel_order ? 1 : 0, d_out, d_cnt + 1);
-      int32_t nout = 0;
-      if (!rc && (hipMemcpyAsync(&nout, d_cnt + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                  fbr_sync(c->stream) != hipSuccess))
-        rc = FBR_ERR_HIP;
-      if (!rc) {
-        out.resize(nout);
-        if (nout && fbr_memcpy_sync(out.data(), d_out, sizeof(float4) * nout, hipMemcpyDeviceToHost) != hipSuccess)
-          rc = FBR_ERR_HIP;
-      }
-    } else {
-      VgArgs a{};
-      a.s[0].in = d_in;
-      a.s[0].stride_in = n;
-      a.s[0].cnt_in = d_cnt;
-      a.s[0].cap = n;
-      a.s[0].out = d_out;
-      a.s[0].stride_out = n;
-      a.s[0].cnt_out = d_cnt + 1;
-      a.s[0].scratch = d_sc;
-      a.s[0].leaf = leaf;
-      a.s[0].nseg = 1;
-      a.s[0].exact = c->P.exact_voxel_order ? 1 : 0;
-      a.err = d_cnt + 2;
-      int32_t ce[2] = {0, 0};  // output count, error word
-      if (hipMemsetAsync(d_cnt + 2, 0, sizeof(int32_t), c->stream) != hipSuccess) rc = FBR_ERR_HIP;
-      if (!rc) launch_voxel_grid(c->stream, a);
-      if (rc || hipMemcpyAsync(ce, d_cnt + 1, sizeof(ce), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-          fbr_sync(c->stream) != hipSuccess || ce[0] < 0 || ce[1] != 0) {
-        rc = FBR_ERR_HIP;
-      } else {
-        const int32_t nout = ce[0];
-        out.resize(nout);
-        if (nout && fbr_memcpy_sync(out.data(), d_out, sizeof(float4) * nout, hipMemcpyDeviceToHost) != hipSuccess)
-          rc = FBR_ERR_HIP;
-      }
-    }
-  }
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_sc);
-  return rc;
+  Dev<float4> d_in, d_out;
+  if (dalloc(d_in, n) || dalloc(d_out, n)) return FBR_ERR_HIP;
+  CK(hipMemcpyAsync(d_in, in, sizeof(float4) * n, hipMemcpyHostToDevice, c->stream));
+  int64_t nout = 0;
+  const int rc = voxel_grid_dev(c, d_in, n, leaf, d_out, &nout);
+  if (rc) return rc;
+  out.resize(nout);
+  if (nout) CK(fbr_memcpy_sync(out.data(), d_out, sizeof(float4) * nout, hipMemcpyDeviceToHost));
+  return FBR_OK;
 }
 
 }  // namespace
@@ -103,24 +55,22 @@ int voxel_grid_dev(fbr_ctx* c, const float4* d_in, int64_t n, float leaf, float4
   *n_out = 0;
   if (n <= 0) return FBR_OK;
   if (n > INT32_MAX / 4) return FBR_ERR_CAPACITY;
-  int32_t* d_cnt = nullptr;
-  uint32_t* d_sc = nullptr;
-  int rc = FBR_OK;
+  // d_cnt: {input count, output count, look-back error word (k_voxel_grid_split: a part that gave
+  // up its look-back flags it, whichever part writes the count)}; the large filter writes its
+  // output count alone and reports a failure itself
+  // the host words of the queued copies stand before the handles, so they outlive every copy: a
+  // handle's release waits for the device
+  const int32_t nn = (int32_t)n;
+  int32_t ce[2] = {0, 0};  // output count, error word
+  Dev<int32_t> d_cnt;
+  Dev<uint32_t> d_sc;
   if (n >= knobs::vg_large_min()) {
-    int32_t nout = 0;
-    if (dalloc(&d_cnt, 1)) return FBR_ERR_HIP;
-    rc = voxel_grid_large(c->stream, c->arena, d_in, n, leaf, 0, c->P.exact_voxel_order ? 1 : 0, d_out, d_cnt);
-    if (!rc && (hipMemcpyAsync(&nout, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                fbr_sync(c->stream) != hipSuccess))
-      rc = FBR_ERR_HIP;
-    *n_out = nout;
-    (void)hipFree(d_cnt);
-    return rc;
-  }
-  if (dalloc(&d_cnt, 3) || dalloc(&d_sc, kVgScratch * n)) {  // input count, output count, error word
-    rc = FBR_ERR_HIP;
+    if (dalloc(d_cnt, 1)) return FBR_ERR_HIP;
+    const int rc = voxel_grid_large(c->stream, c->arena, d_in, n, leaf, 0, c->P.exact_voxel_order ? 1 : 0, d_out, d_cnt);
+    if (rc) return rc;
+    CK(hipMemcpyAsync(ce, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
   } else {
-    int32_t nn = (int32_t)n, ce[2] = {0, 0};
+    if (dalloc(d_cnt, 3) || dalloc(d_sc, kVgScratch * n)) return FBR_ERR_HIP;
     VgArgs a{};
     a.s[0].in = d_in;
     a.s[0].stride_in = n;
@@ -133,21 +83,16 @@ int voxel_grid_dev(fbr_ctx* c, const float4* d_in, int64_t n, float leaf, float4
     a.s[0].leaf = leaf;
     a.s[0].nseg = 1;
     a.s[0].exact = c->P.exact_voxel_order ? 1 : 0;
-    a.err = d_cnt + 2;  // a lost look-back part flags it, whichever part writes the count
-    if (hipMemcpyAsync(d_cnt, &nn, sizeof(int32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemsetAsync(d_cnt + 2, 0, sizeof(int32_t), c->stream) != hipSuccess) {
-      rc = FBR_ERR_HIP;
-    } else {
-      launch_voxel_grid(c->stream, a);
-      if (hipMemcpyAsync(ce, d_cnt + 1, sizeof(ce), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-          fbr_sync(c->stream) != hipSuccess || ce[0] < 0 || ce[1] != 0)
-        rc = FBR_ERR_HIP;
-      *n_out = rc ? 0 : ce[0];
-    }
+    a.err = d_cnt + 2;
+    CK(hipMemcpyAsync(d_cnt, &nn, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    CK(hipMemsetAsync(d_cnt + 2, 0, sizeof(int32_t), c->stream));
+    launch_voxel_grid(c->stream, a);
+    CK(hipMemcpyAsync(ce, d_cnt + 1, sizeof(ce), hipMemcpyDeviceToHost, c->stream));
   }
-  (void)hipFree(d_cnt);
-  (void)hipFree(d_sc);
-  return rc;
+  CK(fbr_sync(c->stream));
+  if (ce[0] < 0 || ce[1] != 0) return FBR_ERR_HIP;
+  *n_out = ce[0];
+  return FBR_OK;
 }
 
 }  // namespace internal
@@ -170,21 +115,18 @@ int build_map_grids(fbr_ctx* c, const float4* d_corner, int64_t nc, const float4
     rc = grid_build_device(c->stream, c->arena, d_corner, nc, invx, inv, true, c->grid_c);
   // block-tile kNN buffers (dense 0.5 m x 0.125 m grids only): per-block arrays for every stream
   // a sub-batch may run on, zeroed once (k_bin_tile re-zeroes the counts it used)
-  (void)hipFree(c->d_bin);
-  c->d_bin = nullptr;
+  c->d_bin.reset();
   c->bin_nb = c->bin_nb_c = 0;
   if (!rc && knn_tile_applies(c->grid_c.g, c->grid_s.g)) {
     c->bin_nb_c = knn_tile_blocks(c->grid_c.g);
     c->bin_nb = c->bin_nb_c + knn_tile_blocks(c->grid_s.g);
     const int64_t slots = (int64_t)c->max_items * 256;
     const bool ok = c->bin_nb < (int64_t)1 << 30 &&
-                    (c->d_fb_list || hipMalloc(&c->d_fb_list, sizeof(int32_t) * 3 * slots) == hipSuccess) &&
-                    hipMalloc(&c->d_bin, sizeof(int32_t) * kMaxSub * 3 * c->bin_nb) == hipSuccess &&
+                    (c->d_fb_list || c->d_fb_list.alloc(3 * slots)) && c->d_bin.alloc(kMaxSub * 3 * c->bin_nb) &&
                     hipMemsetAsync(c->d_bin, 0, sizeof(int32_t) * kMaxSub * 3 * c->bin_nb, c->stream) == hipSuccess;
-    if (!ok) {  // the grid search serves every query
+    if (!ok) {  // the grid search serves every query (alloc() itself reports nothing)
       (void)hipGetLastError();
-      (void)hipFree(c->d_bin);
-      c->d_bin = nullptr;
+      c->d_bin.reset();
       c->bin_nb = c->bin_nb_c = 0;
     }
   }
@@ -209,16 +151,14 @@ int fbr_set_map(fbr_ctx* c, const fbr_point_xyzi* corner, int64_t n_corner, cons
   int rc = voxel_grid_once(c, corner, n_corner, c->P.mapping_corner_leaf_size, c->map_c_host);
   if (!rc) rc = voxel_grid_once(c, surf, n_surf, c->P.mapping_surf_leaf_size, c->map_s_host);
   // the DS maps (map-index order) go to HBM once; the grids are built there
-  float4 *d_c = nullptr, *d_s = nullptr;
+  Dev<float4> d_c, d_s;
   const int64_t nc = (int64_t)c->map_c_host.size(), ns = (int64_t)c->map_s_host.size();
-  if (!rc && (dalloc(&d_c, std::max<int64_t>(nc, 1)) || dalloc(&d_s, std::max<int64_t>(ns, 1)))) rc = FBR_ERR_HIP;
+  if (!rc && (dalloc(d_c, std::max<int64_t>(nc, 1)) || dalloc(d_s, std::max<int64_t>(ns, 1)))) rc = FBR_ERR_HIP;
   if (!rc && nc && hipMemcpy(d_c, c->map_c_host.data(), sizeof(float4) * nc, hipMemcpyHostToDevice) != hipSuccess)
     rc = FBR_ERR_HIP;
   if (!rc && ns && hipMemcpy(d_s, c->map_s_host.data(), sizeof(float4) * ns, hipMemcpyHostToDevice) != hipSuccess)
     rc = FBR_ERR_HIP;
   if (!rc) rc = build_map_grids(c, d_c, nc, d_s, ns);
-  if (d_c) (void)hipFree(d_c);
-  if (d_s) (void)hipFree(d_s);
   c->has_map = rc == FBR_OK;
   return rc;
 }
@@ -303,8 +243,8 @@ int fbr_keyframes_add(fbr_ctx* c, const fbr_keypose* pose, const fbr_point_xyzi*
                       const fbr_point_xyzi* surf, int64_t n_surf) {
   if (!c || !pose || n_corner < 0 || n_surf < 0 || (n_corner && !corner) || (n_surf && !surf)) return FBR_ERR_INVALID_ARG;
   CK(enter(c));
-  int rc = grow(&c->d_kf_c, &c->kf_c_cap, c->kf_c_used + n_corner, c->kf_c_used, c->stream);
-  if (!rc) rc = grow(&c->d_kf_s, &c->kf_s_cap, c->kf_s_used + n_surf, c->kf_s_used, c->stream);
+  int rc = grow(c->d_kf_c, c->kf_c_used + n_corner, c->kf_c_used, c->stream);
+  if (!rc) rc = grow(c->d_kf_s, c->kf_s_used + n_surf, c->kf_s_used, c->stream);
   if (rc) return rc;
   if (n_corner)
     CK(hipMemcpyAsync(c->d_kf_c + c->kf_c_used, corner, sizeof(float4) * n_corner, hipMemcpyHostToDevice, c->stream));
@@ -436,19 +376,18 @@ int fbr_extract_surrounding_keyframes(fbr_ctx* c, double stamp, const fbr_keyfra
   }
   const int nseg_c = (int)(segs.size() / 2);
   if (n_frames) *n_frames = (int32_t)toExtract.size();
-  int rc = grow(&c->d_kraw_c, &c->kraw_c_cap, std::max<int64_t>(tot_c, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_kraw_s, &c->kraw_s_cap, std::max<int64_t>(tot_s, 1), 0, c->stream);
-  if (!rc) rc = grow(&c->d_kf_segs, &c->kf_segs_cap, std::max<int64_t>((int64_t)segs.size(), 1), 0, c->stream);
+  int rc = grow(c->d_kraw_c, std::max<int64_t>(tot_c, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_kraw_s, std::max<int64_t>(tot_s, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_kf_segs, std::max<int64_t>((int64_t)segs.size(), 1), 0, c->stream);
   if (rc) return rc;
   if (!segs.empty())
     CK(hipMemcpyAsync(c->d_kf_segs, segs.data(), sizeof(KfSeg) * segs.size(), hipMemcpyHostToDevice, c->stream));
   launch_kf_transform(c->stream, c->d_kf_c, c->d_kf_segs, nseg_c, max_cnt, c->d_kraw_c);
   launch_kf_transform(c->stream, c->d_kf_s, c->d_kf_segs + nseg_c, (int)segs.size() - nseg_c, max_cnt, c->d_kraw_s);
   CK(hipGetLastError());
-  if (c->d_kds_c) CK(hipFree(c->d_kds_c));
-  if (c->d_kds_s) CK(hipFree(c->d_kds_s));
-  c->d_kds_c = c->d_kds_s = nullptr;
-  if (dalloc(&c->d_kds_c, std::max<int64_t>(tot_c, 1)) || dalloc(&c->d_kds_s, std::max<int64_t>(tot_s, 1))) {
+  c->d_kds_c.reset();
+  c->d_kds_s.reset();
+  if (dalloc(c->d_kds_c, std::max<int64_t>(tot_c, 1)) || dalloc(c->d_kds_s, std::max<int64_t>(tot_s, 1))) {
     (void)fbr_sync(c->stream);  // the pageable copy of `segs` must finish before it goes out of scope
     return FBR_ERR_HIP;
   }

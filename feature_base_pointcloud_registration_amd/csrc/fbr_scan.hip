@@ -172,20 +172,9 @@ int upload_msg(fbr_ctx* c, const fbr_pointcloud2* msg, int32_t* msg_flags, const
   if (c->tail_pending) c->tail_pending = false;  // as upload_scan
   else CK(fbr_sync(c->stream));
   CK(queue_guess(c, guess));
-  if (L.bytes > c->msg_cap) {
-    if (c->d_msg) CK(hipFree(c->d_msg));
-    c->d_msg = nullptr;
-    c->msg_cap = 0;
-    CK(hipMalloc(&c->d_msg, L.bytes));
-    c->msg_cap = L.bytes;
-  }
-  if (L.bytes > c->h_msg_cap) {
-    if (c->h_msg) CK(hipHostFree(c->h_msg));
-    c->h_msg = nullptr;
-    c->h_msg_cap = 0;
-    CK(hipHostMalloc((void**)&c->h_msg, L.bytes, hipHostMallocDefault));
-    c->h_msg_cap = L.bytes;
-  }
+  // nothing of the old message is kept: the old block goes first, the new one has the message's size
+  if ((int64_t)L.bytes > c->d_msg.cap() && !c->d_msg.alloc((int64_t)L.bytes)) return alloc_failed();
+  if ((int64_t)L.bytes > c->h_msg.cap() && !c->h_msg.alloc((int64_t)L.bytes)) return alloc_failed();
   if (L.bytes) {
     CK(pinned_upload_async(c->dev, c->d_msg, c->h_msg, msg->data, L.bytes, c->stream));
   }

@@ -1,0 +1,211 @@
+"""Who releases what the host units allocate: the owning handles of csrc/fbr_own.h.
+
+CPU: tests/native/own_check.cpp instantiates the header over a counting malloc / free policy and
+checks the handle semantics under AddressSanitizer and UBSan, as a stand-alone program.
+
+GPU: fbr_diag_live_resources counts the device blocks, pinned blocks, streams and events the
+process's contexts and communicators hold.  Each test runs in a child process (no other context
+alive), reads the counters before Context(...) and after close(), and drives C1 (16 x 1800) with
+max_batch = 2.
+"""
+import json
+import os
+import subprocess
+import sys
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(REPO, "feature_base_pointcloud_registration_amd", "csrc")
+NATIVE = os.path.join(REPO, "tests", "native")
+
+
+def test_owning_handles_under_sanitizers():
+    """Alloc / destruct, moves, the growable form's rule and its two failure paths, and a struct of
+    five handles whose k-th allocation fails: own_check exits 0 only if all of them hold, with
+    LeakSanitizer and the double-free check behind every case."""
+    out_dir = os.path.join(NATIVE, "build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "own_check")
+    # the sanitizer runtimes are linked statically: the program runs in whatever environment the suite has
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-I", CSRC, "-o", exe,
+                           os.path.join(NATIVE, "own_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "own_check: ok" in r.stdout
+
+
+def run_child(script, env_set=None):
+    env = dict(os.environ)
+    env.update(env_set or {})
+    r = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=240, env=env, cwd=REPO)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+
+LIFE_CYCLE = """
+import ctypes, json
+import numpy as np
+from feature_base_pointcloud_registration_amd import api, synth
+from feature_base_pointcloud_registration_amd.fbr_types import (KEYPOSE, POINT_XYZI, PointCloud2, default_params,
+                                                                icp_params, keyframe_params)
+
+def cloud(pts, n, seed):  # n points of a scan as a lidar-frame feature cloud
+    idx = np.sort(np.random.default_rng(seed).choice(len(pts), n, replace=False))
+    out = np.zeros(n, POINT_XYZI)
+    for f in ("x", "y", "z"):
+        out[f] = pts[f][idx]
+    return out
+
+P = default_params(16, 1800, max_batch=2)
+jobs = synth.make_jobs("C1", 3, base_seed=5200)
+scans, guesses = [j[0] for j in jobs], np.stack([j[1] for j in jobs])
+cmap, smap = synth.config_map("C1")
+base = api.live_resources()
+ctx = api.Context(P)
+alive = api.live_resources()
+ctx.set_map(cmap, smap)
+ctx.process_scan(scans[0], 0.0, guesses[0])
+velodyne = np.dtype({"names": ["x", "y", "z", "intensity", "ring", "time"], "itemsize": 32,
+                     "formats": ["<f4", "<f4", "<f4", "<f4", "<u2", "<f4"], "offsets": [0, 4, 8, 16, 20, 24]})
+for k, n in enumerate((len(scans[0]) // 2, len(scans[0]))):  # the second message is larger: d_msg / h_msg grow
+    rec = np.zeros(n, velodyne)
+    for f in velodyne.names:
+        rec[f] = scans[0][f][:n]
+    ctx.process_msg(PointCloud2.from_array(rec), 1.0 + k, guesses[0])
+ctx.batch_stage(scans[:2], guesses[:2])  # allocates d_pk
+ctx.batch_launch()
+ctx.batch_wait()
+ctx.batch_results()
+ctx.process_batch(scans, guesses)  # the ingest: two device batches, both input slots
+q = synth.imu_queue(10.0 - 0.05, 10.0 + 0.16)
+table, _ = api.imu_deskew_info(q, 10.0, 10.1)
+assert table["imu_available"] == 1
+ctx.set_deskew([table])  # allocates d_desk
+ctx.process_scan(scans[1], 10.0, guesses[1])
+ctx.set_deskew(None)
+ctx.feature_paths()
+ctx.feature_paths()
+stamps = api.lib().fbr_diag_feature_stamps
+stamps.restype, stamps.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]
+assert stamps(ctx._h, None) == 0
+small = ctx.voxel_grid(cloud(scans[0], 500, 3), 0.4)    # below FBR_VG_LARGE_MIN (2048 in this process)
+large = ctx.voxel_grid(cloud(scans[0], 4000, 4), 0.4)   # above it
+assert 0 < len(small) <= 500 and 0 < len(large) <= 4000
+ctx.set_profiling(True)
+ctx.process_scan(scans[2], 20.0, guesses[2])
+ms, launches = ctx.kernel_time("project")
+for k in range(3):  # 600 + 600 points outgrow the store's first capacity of 1024
+    gt = jobs[k][2]
+    pose = np.array((gt[3], gt[4], gt[5], k, gt[0], gt[1], gt[2], 0.0, 2.0 * k), KEYPOSE)
+    ctx.keyframes_add(pose, cloud(scans[k], 600, 10 + k), cloud(scans[k], 600, 20 + k))
+n_map = ctx.extract_surrounding_keyframes(5.0, keyframe_params())
+src = cloud(scans[0], 300, 30)
+tgt = src.copy()
+tgt["x"] += 0.1
+icp = ctx.icp_align(src, tgt, icp_params())
+mid = api.live_resources()
+ctx.close()
+print(json.dumps(dict(base=base, alive=alive, mid=mid, end=api.live_resources(), n_map=n_map, launches=launches)))
+"""
+
+
+@pytest.mark.gpu
+def test_whole_life_cycle_returns_to_baseline():
+    """Every path that allocates on demand, then close(): all four counters are back at their values
+    from before the create.  fbr_create itself holds 51 device arrays and 7 pinned blocks (its
+    allocation chain, unchanged), at least two streams and five events; with the arrays allocated
+    on demand the living context is above the baseline by more than 55 device blocks."""
+    r = run_child(LIFE_CYCLE, {"FBR_VG_LARGE_MIN": "2048"})
+    assert all(v >= 0 for v in r["base"])
+    created = [a - b for a, b in zip(r["alive"], r["base"])]
+    assert created[:2] == [51, 7] and created[2] >= 2 and created[3] >= 5
+    assert r["mid"][0] - r["base"][0] >= 55
+    assert all(m >= a for m, a in zip(r["mid"], r["alive"]))
+    assert r["launches"] > 0 and r["n_map"][2] > 0
+    assert r["end"] == r["base"]
+
+
+TWO_CONTEXTS = """
+import json
+from feature_base_pointcloud_registration_amd import api
+from feature_base_pointcloud_registration_amd.fbr_types import default_params
+base = api.live_resources()
+a = api.Context(default_params(16, 1800, max_batch=2))
+one = api.live_resources()
+b = api.Context(default_params(16, 1800, max_batch=2))
+two = api.live_resources()
+a.close()
+after_a = api.live_resources()
+b.close()
+print(json.dumps(dict(base=base, one=one, two=two, after_a=after_a, end=api.live_resources())))
+"""
+
+
+@pytest.mark.gpu
+def test_two_contexts_closed_in_creation_order():
+    r = run_child(TWO_CONTEXTS)
+    per_ctx = [o - b for o, b in zip(r["one"], r["base"])]
+    assert per_ctx[:2] == [51, 7]
+    assert [t - o for t, o in zip(r["two"], r["one"])] == per_ctx
+    assert r["after_a"] == [t - p for t, p in zip(r["two"], per_ctx)]
+    assert r["end"] == r["base"]
+
+
+CREATE_FAILS = """
+import ctypes, json
+from feature_base_pointcloud_registration_amd import api
+from feature_base_pointcloud_registration_amd.fbr_types import default_params
+P = default_params(16, 1800, max_batch=512, max_points_per_scan=2**31 - 1)
+base = api.live_resources()
+h = ctypes.c_void_p()
+rc = api.lib().fbr_create(ctypes.byref(h), ctypes.byref(P), 0)
+print(json.dumps(dict(base=base, rc=rc, handle=h.value or 0, end=api.live_resources())))
+"""
+
+
+@pytest.mark.gpu
+def test_create_fails_cleanly():
+    """fbr_create's first device request is one hipMalloc of 2^40 points (24 TiB), which the runtime
+    refuses at once: nothing is filled.  fbr_params.max_points_per_scan is an int32, so the 2^40
+    points are 512 scans of 2^31 - 1.  The call returns FBR_ERR_HIP and the counters are at the
+    baseline: the streams and events created before the failure went with the context."""
+    r = run_child(CREATE_FAILS)
+    assert r["rc"] == -2 and r["handle"] == 0
+    assert r["end"] == r["base"]
+
+
+COMM = """
+import ctypes, json
+from feature_base_pointcloud_registration_amd import api
+from feature_base_pointcloud_registration_amd.fbr_types import default_params
+L = api.lib()
+ctx = api.Context(default_params(16, 1800, max_batch=2))
+base = api.live_resources()
+out = (ctypes.c_void_p * 1)()
+ctxs = (ctypes.c_void_p * 1)(ctx._h)
+rc_local = L.fbr_comm_create_local(out, ctxs, 1, 8)
+held = api.live_resources()
+rc_destroy = L.fbr_comm_destroy(out[0]) if rc_local == 0 else None
+after_local = api.live_resources()
+uid = (ctypes.c_uint8 * 128)()
+m = ctypes.c_void_p()
+rc_small = L.fbr_comm_create(ctypes.byref(m), ctx._h, uid, 1, 0, 1)  # max_jobs_per_rank 1 < max_batch 2
+after_small = api.live_resources()
+ctx.close()
+print(json.dumps(dict(base=base, rc_local=rc_local, held=held, rc_destroy=rc_destroy, after_local=after_local,
+                      rc_small=rc_small, handle=m.value or 0, after_small=after_small)))
+"""
+
+
+@pytest.mark.gpu
+def test_communicator_returns_to_baseline():
+    """fbr_comm_create_local over one context, then destroy: the send block and the two events are
+    gone.  fbr_comm_create with max_jobs_per_rank < max_batch: FBR_ERR_CAPACITY, nothing held."""
+    r = run_child(COMM)
+    assert r["rc_local"] == 0 and r["rc_destroy"] == 0
+    assert [h - b for h, b in zip(r["held"], r["base"])] == [1, 0, 0, 2]
+    assert r["after_local"] == r["base"]
+    assert r["rc_small"] == -4 and r["handle"] == 0
+    assert r["after_small"] == r["base"]
