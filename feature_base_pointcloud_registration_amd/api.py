@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
-                        FbrLoopResult, FbrParams, FbrRegStats, PointCloud2, default_params, icp_params, loop_params, ptr)
+                        FbrLoopResult, FbrParams, FbrRegStats, FbrScMatch, PointCloud2, default_params, icp_params,
+                        loop_params, ptr, sc_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -37,6 +38,8 @@ EXPORTED_SYMBOLS = [
     "fbr_keyframe_params_default", "fbr_keyframes_add", "fbr_keyframes_set_pose", "fbr_keyframes_count",
     "fbr_keyframes_reset", "fbr_extract_surrounding_keyframes",
     "fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align", "fbr_selftest_nn1",
+    "fbr_sc_params_default", "fbr_sc_describe", "fbr_sc_update", "fbr_sc_descriptor", "fbr_sc_query",
+    "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -126,6 +129,13 @@ def lib():
             "fbr_perform_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP]),
             "fbr_icp_align": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP]),
             "fbr_selftest_nn1": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, ctypes.c_float, _VP, _VP]),
+            "fbr_sc_params_default": (None, [_VP]),
+            "fbr_sc_describe": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+            "fbr_sc_update": (ctypes.c_int, [_VP, _VP, _VP]),
+            "fbr_sc_descriptor": (ctypes.c_int, [_VP, _I64, _VP]),
+            "fbr_sc_query": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, ctypes.c_int, _VP, _VP]),
+            "fbr_sc_detect_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
+            "fbr_perform_loop_closure_sc": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP, _VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
             "fbr_comm_create_local": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int]),
@@ -569,6 +579,84 @@ class Context:
                                       ptr(query) if len(query) else None, len(query), ctypes.c_float(max_distance),
                                       ptr(idx), ptr(d2)), "fbr_selftest_nn1")
         return idx[:len(query)].copy(), d2[:len(query)].copy()
+
+    # ---- place recognition (include/fbr.h "place recognition") ----
+    def sc_describe(self, corner, surf, sc=None):
+        """The scan-context descriptor of a lidar-frame cloud (corner then surf): float32 [n_ring, n_sector]."""
+        sp = sc if sc is not None else sc_params()
+        corner = _as_points(corner, POINT_XYZI)
+        surf = _as_points(surf, POINT_XYZI)
+        out = np.zeros((sp.n_ring, sp.n_sector), np.float32)
+        _check(lib().fbr_sc_describe(self._h, ctypes.byref(sp), ptr(corner) if len(corner) else None, len(corner),
+                                     ptr(surf) if len(surf) else None, len(surf), ptr(out)), "fbr_sc_describe")
+        return out
+
+    def sc_update(self, sc=None):
+        """Describe the keyframes added since the last call; returns how many."""
+        sp = sc if sc is not None else sc_params()
+        n = _I64()
+        _check(lib().fbr_sc_update(self._h, ctypes.byref(sp), ctypes.byref(n)), "fbr_sc_update")
+        return n.value
+
+    def sc_descriptor(self, keyframe, sc=None):
+        """The stored descriptor of one keyframe (`sc`: the shape the store was described with)."""
+        sp = sc if sc is not None else sc_params()
+        out = np.zeros((sp.n_ring, sp.n_sector), np.float32)
+        _check(lib().fbr_sc_descriptor(self._h, int(keyframe), ptr(out)), "fbr_sc_descriptor")
+        return out
+
+    def sc_query(self, corner, surf, k=4, sc=None, raw=False):
+        """The min(k, keyframes) best matches of a lidar-frame cloud in rank order, as dicts (raw: the
+        FbrScMatch array and its length)."""
+        sp = sc if sc is not None else sc_params()
+        corner = _as_points(corner, POINT_XYZI)
+        surf = _as_points(surf, POINT_XYZI)
+        out = (FbrScMatch * max(int(k), 1))()
+        n = ctypes.c_int()
+        _check(lib().fbr_sc_query(self._h, ctypes.byref(sp), ptr(corner) if len(corner) else None, len(corner),
+                                  ptr(surf) if len(surf) else None, len(surf), int(k), out, ctypes.byref(n)),
+               "fbr_sc_query")
+        return (out, n.value) if raw else [out[i].as_dict() for i in range(n.value)]
+
+    def sc_detect_loop_closure(self, stamp, lparams=None, sc=None):
+        """detectLoopClosure by appearance: ((latest_id, closest_id) or None, the best candidate's match
+        as a dict or None when there was no candidate at all)."""
+        lp = lparams if lparams is not None else loop_params()
+        sp = sc if sc is not None else sc_params()
+        a, b, m = _I32(), _I32(), FbrScMatch()
+        _check(lib().fbr_sc_detect_loop_closure(self._h, ctypes.c_double(stamp), ctypes.byref(lp), ctypes.byref(sp),
+                                                ctypes.byref(a), ctypes.byref(b), ctypes.byref(m)),
+               "fbr_sc_detect_loop_closure")
+        return (None if a.value < 0 else (a.value, b.value)), (None if m.keyframe < 0 else m.as_dict())
+
+    def perform_loop_closure_sc(self, stamp, lparams=None, sc=None, raw=False):
+        """perform_loop_closure with the candidate and the last keyframe's pose taken from the scan-context
+        match: (fbr_loop_result, match), dicts unless raw."""
+        lp = lparams if lparams is not None else loop_params()
+        sp = sc if sc is not None else sc_params()
+        r, m = FbrLoopResult(), FbrScMatch()
+        _check(lib().fbr_perform_loop_closure_sc(self._h, ctypes.c_double(stamp), ctypes.byref(lp), ctypes.byref(sp),
+                                                 ctypes.byref(r), ctypes.byref(m)), "fbr_perform_loop_closure_sc")
+        return (r, m) if raw else (r.as_dict(), None if m.keyframe < 0 else m.as_dict())
+
+    def relocalize(self, points, k=4, sc=None):
+        """Find the pose of one raw scan (POINT_XYZIRT) without a guess: project, extract features,
+        down-sample them at the two mapping leaves, sc_query, then register from each hypothesis in
+        rank order against the installed registration map (set_map / load_map; the keyframes serve only
+        as the place database).  Returns (hypotheses, winner): hypotheses = [(match, pose, stats)] and
+        winner = the index of the converged, non-degenerate result with the largest n_sel (the first
+        of equals), or -1."""
+        f = self.features(points)
+        corner = self.voxel_grid(f["corner"], self.params.mapping_corner_leaf_size)
+        surf = self.voxel_grid(f["surf"], self.params.mapping_surf_leaf_size)
+        hyps, winner = [], -1
+        for m in self.sc_query(corner, surf, k, sc):
+            pose, st = self.register(f["corner"], f["surf"], m["pose_guess"])
+            hyps.append((m, pose, st))
+            if st["status"] == 0 and st["converged"] and not st["degenerate"] and (
+                    winner < 0 or st["n_sel"] > hyps[winner][2]["n_sel"]):
+                winner = len(hyps) - 1
+        return hyps, winner
 
     @property
     def stream_handle(self):

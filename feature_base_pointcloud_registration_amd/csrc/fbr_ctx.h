@@ -8,6 +8,7 @@
 //   fbr_comm.hip    RCCL communicator and pose gather
 //   fbr_map.hip     map VoxelGrid and kNN grids, keyframe store and local map, pose helpers
 //   fbr_loop.hip    loop closure candidate search and ICP
+//   fbr_sc.hip      scan-context place recognition: descriptor store, search, loop closure under drift
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -443,6 +444,20 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   unsigned long long icp_gen = 0;
   DevGrid icp_grid;            // the ICP's own grid over its target
 
+  // ---- scan-context place recognition (fbr_sc.hip) ----
+  // One descriptor per keyframe, in keyframe order, described on demand (fbr_sc_update) from the
+  // keyframe pools above; fbr_keyframes_reset (fbr_map.hip) and a change of sc_P empty the store.
+  fbr_sc_params sc_P{};           // the parameters the store was described with (sc_n > 0)
+  int64_t sc_n = 0;               // keyframes described so far
+  GrowDev<uint32_t> d_sc_desc;    // [keyframes][n_ring][n_sector] float bits, grown on demand
+  GrowDev<double> d_sc_norm;      // [keyframes][n_sector] column norms
+  GrowDev<ScSeg> d_sc_segs;       // a describe launch's segments
+  GrowDev<ScRec> d_sc_rec;        // [keyframes] a search's per-candidate records
+  GrowPinned<ScRec> h_sc_rec;     // the pinned result block: the records of the last search
+  Dev<uint32_t> d_sc_q;           // the query slot: one descriptor of the largest shape
+  Dev<double> d_sc_qn;            // ... and its column norms
+  GrowDev<float4> d_sc_cloud;     // an uploaded query cloud, corner then surf
+
   // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;
   std::set<std::string> profile_only;  // empty: time every kernel
@@ -456,6 +471,19 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
 
 namespace fbr {
 namespace internal __attribute__((visibility("hidden"))) {
+
+// A * B of two affine row-major 4x4 float matrices (Eigen::Affine3f product): entries
+// ((a0 b0 + a1 b1) + a2 b2), the translation column + a3.
+inline void affine_mul(const float* A, const float* B, float* G) {
+  for (int r = 0; r < 3; ++r)
+    for (int q = 0; q < 4; ++q) {
+      float s = (A[4 * r] * B[q] + A[4 * r + 1] * B[4 + q]) + A[4 * r + 2] * B[8 + q];
+      if (q == 3) s = s + A[4 * r + 3];
+      G[4 * r + q] = s;
+    }
+  G[12] = G[13] = G[14] = 0.0f;
+  G[15] = 1.0f;
+}
 
 // Every public entry point: the context's device, and no single-scan tail left on the stream
 // unless the call is a single scan itself (keep_tail: its work is ordered after the tail).
@@ -493,6 +521,12 @@ int check_err(fbr_ctx* c, int B);
 int drop_staged_batch(fbr_ctx* c);
 // fbr_map.hip
 int voxel_grid_dev(fbr_ctx* c, const float4* d_in, int64_t n, float leaf, float4* d_out, int64_t* n_out);
+// fbr_loop.hip
+bool loop_params_ok(const fbr_loop_params* lp);
+// performLoopClosure for a given candidate pair; latest_pose (null: the stored one) stands for the
+// last keyframe's pose wherever performLoopClosure reads it
+int loop_perform(fbr_ctx* c, const fbr_loop_params* lp, int32_t latest, int32_t closest, const float* latest_pose,
+                 fbr_loop_result* out);
 
 }  // namespace internal
 }  // namespace fbr

@@ -431,4 +431,26 @@ void launch_icp_far(hipStream_t s, const IcpArgs& a, int mode);
 void launch_icp_solve(hipStream_t s, const IcpArgs& a, int max_iter, double teps, double feps, unsigned long long gen);
 void launch_icp_finish(hipStream_t s, const IcpArgs& a, fbr_icp_result* out);
 
+// ---- scan-context place recognition (k_scancontext.hip) ----
+struct ScPools {             // the clouds a segment may lie in
+  const float4* p[3];        // keyframe corner pool, keyframe surf pool, an uploaded query cloud
+};
+struct ScSeg {               // one cloud: pools.p[pool][src .. src+count) -> descriptor slot `slot`
+  int64_t src, count, slot;
+  int32_t pool, pad;
+};
+struct ScRec {               // a candidate's match: min over the shifts, ties to the lowest shift
+  double distance;
+  int32_t shift, pad;
+};
+constexpr int64_t kScMaxCloud = (int64_t)65535 * 4096;  // points of one described cloud
+// desc: [slots][n_ring][n_sector] bits of non-negative floats, the slots written zeroed beforehand
+void launch_sc_describe(hipStream_t s, const ScPools& pools, const ScSeg* segs, int nseg, int64_t max_count, int n_ring,
+                        int n_sector, float max_radius, float lidar_height, uint32_t* desc);
+// norms: [nslots][n_sector] column norms of desc's first nslots slots
+void launch_sc_norms(hipStream_t s, const uint32_t* desc, int64_t nslots, int n_ring, int n_sector, double* norms);
+// rec[i] = the match of the query against stored descriptor i, i < n
+void launch_sc_search(hipStream_t s, const uint32_t* qdesc, const double* qnorm, const uint32_t* desc, const double* norms,
+                      int64_t n, int n_ring, int n_sector, ScRec* rec);
+
 }  // namespace fbr

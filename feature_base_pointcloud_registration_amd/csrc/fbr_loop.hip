@@ -158,49 +158,25 @@ void pose3_double(const float p[6], double m[12]) {
 
 }  // namespace
 
-extern "C" {
+namespace fbr {
+namespace internal {
 
-void fbr_loop_params_default(fbr_loop_params* p) {
-  if (!p) return;
-  std::memset(p, 0, sizeof(*p));
-  p->search_radius = 15.0f;     // params.yaml:72-75
-  p->search_time_diff = 30.0f;
-  p->search_num = 25;
-  p->fitness_score = 0.3f;
-  p->icp_leaf_size = 0.0f;      // downSizeFilterICP: mappingSurfLeafSize (mapOptmization.h:192)
-  p->icp.max_correspondence_distance = 100.0f;  // mapOptmization.h:690-693
-  p->icp.max_iterations = 100;
-  p->icp.transformation_epsilon = 1e-6;
-  p->icp.euclidean_fitness_epsilon = 1e-6;
+bool loop_params_ok(const fbr_loop_params* lp) {
+  return lp && lp->search_radius >= 0 && lp->search_num >= 0 && lp->icp_leaf_size >= 0 && icp_params_ok(lp->icp);
 }
 
-int fbr_detect_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp, int32_t* latest_id, int32_t* closest_id) {
-  if (!c || !lp || !latest_id || !closest_id || !(lp->search_radius >= 0)) return FBR_ERR_INVALID_ARG;
-  CK(enter(c));
-  (void)loop_candidate(c, stamp, lp, latest_id, closest_id);
-  return FBR_OK;
-}
-
-int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp, fbr_loop_result* out) {
-  if (!c || !lp || !out || !(lp->search_radius >= 0) || lp->search_num < 0 || !(lp->icp_leaf_size >= 0) ||
-      !icp_params_ok(lp->icp))
-    return FBR_ERR_INVALID_ARG;
-  CK(enter(c));
-  std::memset(out, 0, sizeof(*out));
-  out->status = FBR_LOOP_NO_CANDIDATE;
-  out->latest_id = out->closest_id = -1;
-  int32_t latest, closest;
-  if (!loop_candidate(c, stamp, lp, &latest, &closest)) return FBR_OK;
+int loop_perform(fbr_ctx* c, const fbr_loop_params* lp, int32_t latest, int32_t closest, const float* latest_pose,
+                 fbr_loop_result* out) {
   // latestKeyFrameCloud (:650-651) and nearHistoryKeyFrameCloud (:656-665): transformPointCloud of
   // the stored clouds, corner then surf per keyframe.  Segments by pool: [source corner, target
   // corners..., source surf, target surfs...]
   std::vector<KfSeg> cseg, sseg;
   int64_t n_src = 0, n_raw = 0, max_cnt = 0;
-  auto add = [&](int k, int64_t* off) {
+  auto add = [&](int k, int64_t* off, const float* tr_override) {
     const fbr_keypose& pose = c->kf_poses[k];
     const float tr[6] = {pose.roll, pose.pitch, pose.yaw, pose.x, pose.y, pose.z};
     float m[16];
-    fbr_affine_from_pose(tr, m);
+    fbr_affine_from_pose(tr_override ? tr_override : tr, m);
     KfSeg g;
     for (int q = 0; q < 12; ++q) g.T[q] = m[q];
     g.src = c->kf_c_off[k];
@@ -216,10 +192,10 @@ int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp
     sseg.push_back(g);
     max_cnt = std::max(max_cnt, g.count);
   };
-  add(latest, &n_src);
+  add(latest, &n_src, latest_pose);
   for (int64_t k = (int64_t)closest - lp->search_num; k <= (int64_t)closest + lp->search_num; ++k) {
     if (k < 0 || k > latest) continue;  // :659
-    add((int)k, &n_raw);
+    add((int)k, &n_raw, nullptr);
   }
   const int nseg = (int)cseg.size();  // 1 source segment + the target's, per pool
   std::vector<KfSeg> segs(cseg);
@@ -253,17 +229,10 @@ int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp
   // tCorrect = correctionLidarFrame * tWrong (:729-741), Eigen::Affine3f product in float
   const fbr_keypose& kl = c->kf_poses[latest];
   const fbr_keypose& kc = c->kf_poses[closest];
-  const float wrong[6] = {kl.roll, kl.pitch, kl.yaw, kl.x, kl.y, kl.z};
-  float W[16], G[16] = {0};
-  fbr_affine_from_pose(wrong, W);
-  const float* C = out->icp.transform;
-  for (int r = 0; r < 3; ++r)
-    for (int q = 0; q < 4; ++q) {
-      float s = (C[4 * r] * W[q] + C[4 * r + 1] * W[4 + q]) + C[4 * r + 2] * W[8 + q];
-      if (q == 3) s = s + C[4 * r + 3];
-      G[4 * r + q] = s;
-    }
-  G[15] = 1.0f;
+  const float stored[6] = {kl.roll, kl.pitch, kl.yaw, kl.x, kl.y, kl.z};
+  float W[16], G[16];
+  fbr_affine_from_pose(latest_pose ? latest_pose : stored, W);
+  affine_mul(out->icp.transform, W, G);
   fbr_pose_from_affine(G, out->pose_corrected);
   const float to[6] = {kc.roll, kc.pitch, kc.yaw, kc.x, kc.y, kc.z};
   std::memcpy(out->pose_closest, to, sizeof(to));
@@ -280,6 +249,43 @@ int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp
   out->between[12] = out->between[13] = out->between[14] = 0.0f;
   out->between[15] = 1.0f;
   return FBR_OK;
+}
+
+}  // namespace internal
+}  // namespace fbr
+
+extern "C" {
+
+void fbr_loop_params_default(fbr_loop_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->search_radius = 15.0f;     // params.yaml:72-75
+  p->search_time_diff = 30.0f;
+  p->search_num = 25;
+  p->fitness_score = 0.3f;
+  p->icp_leaf_size = 0.0f;      // downSizeFilterICP: mappingSurfLeafSize (mapOptmization.h:192)
+  p->icp.max_correspondence_distance = 100.0f;  // mapOptmization.h:690-693
+  p->icp.max_iterations = 100;
+  p->icp.transformation_epsilon = 1e-6;
+  p->icp.euclidean_fitness_epsilon = 1e-6;
+}
+
+int fbr_detect_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp, int32_t* latest_id, int32_t* closest_id) {
+  if (!c || !lp || !latest_id || !closest_id || !(lp->search_radius >= 0)) return FBR_ERR_INVALID_ARG;
+  CK(enter(c));
+  (void)loop_candidate(c, stamp, lp, latest_id, closest_id);
+  return FBR_OK;
+}
+
+int fbr_perform_loop_closure(fbr_ctx* c, double stamp, const fbr_loop_params* lp, fbr_loop_result* out) {
+  if (!c || !out || !loop_params_ok(lp)) return FBR_ERR_INVALID_ARG;
+  CK(enter(c));
+  std::memset(out, 0, sizeof(*out));
+  out->status = FBR_LOOP_NO_CANDIDATE;
+  out->latest_id = out->closest_id = -1;
+  int32_t latest, closest;
+  if (!loop_candidate(c, stamp, lp, &latest, &closest)) return FBR_OK;
+  return loop_perform(c, lp, latest, closest, nullptr, out);
 }
 
 int fbr_icp_align(fbr_ctx* c, const fbr_point_xyzi* source, int64_t n_source, const fbr_point_xyzi* target,

@@ -288,6 +288,7 @@ int fbr_keyframes_reset(fbr_ctx* c) {
   c->kf_s_off.clear();
   c->kf_s_cnt.clear();
   c->kf_c_used = c->kf_s_used = 0;
+  c->sc_n = 0;  // the scan-context descriptors go with their keyframes (fbr_sc.hip)
   return FBR_OK;
 }
 

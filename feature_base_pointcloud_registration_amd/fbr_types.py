@@ -114,6 +114,28 @@ def loop_params(icp=None, **kw):
     return p
 
 
+# place recognition (include/fbr.h "place recognition")
+FBR_SC_MAX_K = 16
+
+
+class FbrScParams(_Dictable):
+    _fields_ = [("n_ring", ctypes.c_int32), ("n_sector", ctypes.c_int32), ("max_radius", ctypes.c_float),
+                ("lidar_height", ctypes.c_float), ("dist_threshold", ctypes.c_float), ("reserved_", ctypes.c_int32 * 3)]
+
+
+class FbrScMatch(_Dictable):
+    _fields_ = [("keyframe", ctypes.c_int32), ("shift", ctypes.c_int32), ("distance", ctypes.c_double),
+                ("pose_guess", ctypes.c_float * 6), ("pad_", ctypes.c_float * 2)]
+
+
+def sc_params(**kw):
+    """fbr_sc_params_default: 20 rings x 60 sectors over 80 m, lidar height 2 m, dist_threshold 0.2."""
+    p = FbrScParams(20, 60, 80.0, 2.0, 0.2)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

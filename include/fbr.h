@@ -412,6 +412,109 @@ int fbr_icp_align(fbr_ctx* ctx, const fbr_point_xyzi* source, int64_t n_source, 
 int fbr_selftest_nn1(fbr_ctx* ctx, const fbr_point_xyzi* target, int64_t n_target, const fbr_point_xyzi* query,
                      int64_t n_query, float max_distance, int32_t* index, float* d2);
 
+/* ---- place recognition: scan-context descriptors and search ---------------------
+ * The registration path needs a pose guess near the truth, and fbr_detect_loop_closure needs the
+ * last keyframe's stored pose within search_radius of the place it revisits.  The calls below find
+ * the place from the clouds alone: every keyframe's lidar-frame corner + surf cloud (already in HBM,
+ * fbr_keyframes_add) gets a Scan Context descriptor (Kim & Kim, IROS 2018), and a query is compared
+ * with every stored descriptor at every column shift on the device: the exact minimum, no ring-key
+ * shortlist, no shift window.
+ *
+ * This is the project's own restatement of Scan Context.  It is not pinned against any
+ * third-party code (neither the authors' nor SC-LIO-SAM's), and the reference has no counterpart.
+ *
+ * Descriptor D[n_ring][n_sector] (float) of a cloud, in float, operation by operation
+ * (csrc/fbr_sc.h, compiled for the device and for the CPU probe of the tests; no FMA contraction):
+ *   r      = sqrt(x * x + y * y), correctly rounded
+ *   a point counts iff x, y, z are finite and r < max_radius (r == max_radius is dropped; the
+ *          largest float below max_radius lands in the last ring)
+ *   ring   = min(n_ring - 1, (int)floorf((r / max_radius) * (float)n_ring))
+ *   theta  = atan2f(y, x) (glibc's, csrc/fbr_fdlibm.h); if (theta < 0) theta = theta + (float)(2 pi)
+ *          (x > 0, y = +-0: theta = 0, sector 0; x < 0, y = +0 or -0: theta = +pi or -pi + 2 pi,
+ *          both sector n_sector / 2 for an even n_sector)
+ *   sector = min(n_sector - 1, (int)floorf((theta / (float)(2 pi)) * (float)n_sector))
+ *   D[ring][sector] = the maximum of max(z + lidar_height, 0) over the cell's points; an empty
+ *          cell is 0.
+ * The descriptor does not depend on the order of the points.  A keyframe's descriptor is built
+ * from its corner cloud followed by its surf cloud.
+ *
+ * Distance of a query Q to a candidate C at shift s in [0, n_sector):
+ *   columns c = 0 .. n_sector - 1 ascending; norm(X, c) = sqrt of the double sum over the rings
+ *   (ascending) of X[r][c]^2; a column counts only where norm(Q, c) > 0 and norm(C, (c + s) mod
+ *   n_sector) > 0; cos_c = (sum_r Q[r][c] C[r][(c + s) mod n_sector]) / (norm(Q, c) norm(C, (c + s)
+ *   mod n_sector)), sums in double with the rings ascending (the device multiplies by the two inverse
+ *   norms, a difference of a few double ulps); d(s) = 1 - (sum_c cos_c) / n_eff, or 1.0 when no
+ *   column counts.
+ *   A candidate's match is min_s d(s), ties to the lowest shift; candidates rank by (distance,
+ *   keyframe index) ascending.
+ *
+ * Pose hypothesis of a match: delta = (float)(shift * 2 pi / n_sector) (the product in double),
+ *   pose_guess = fbr_pose_from_affine(fbr_affine_from_pose(stored pose of the keyframe) *
+ *   fbr_affine_from_pose({0, 0, delta, 0, 0, 0})) with the float product of the loop closure's
+ *   tCorrect: the sensor at the keyframe's position, turned about its own z by delta.  A scan taken
+ *   at a keyframe's position with its yaw increased by delta matches at shift ~ delta n_sector / 2 pi.
+ *
+ * Two calls on the same input return the same bytes (integer maxima, fixed summation orders, no
+ * float or double atomics).
+ *
+ * dist_threshold: the default 0.2 lies between the true matches (<= 0.17) and the nearest false
+ * ones (>= 0.23) seen on the project's synthetic fixtures.  It has not been measured on real data. */
+typedef struct fbr_sc_params {
+  int32_t n_ring;        /* 20, 1..32 */
+  int32_t n_sector;      /* 60, 2..64 */
+  float max_radius;      /* 80 m */
+  float lidar_height;    /* 2.0 m, added to z so that ground returns are positive */
+  float dist_threshold;  /* loop acceptance; default 0.2 (see above) */
+  int32_t reserved_[3];
+} fbr_sc_params;
+
+typedef struct fbr_sc_match {
+  int32_t keyframe, shift;   /* keyframe -1: no candidate */
+  double distance;
+  float pose_guess[6];       /* [roll, pitch, yaw, x, y, z] */
+  float pad_[2];
+} fbr_sc_match;
+
+#define FBR_SC_MAX_K 16
+
+void fbr_sc_params_default(fbr_sc_params* p);
+/* Diagnostic, and the query's first half: the descriptor of a host cloud (corner then surf), built
+ * on the device.  desc_out [n_ring * n_sector], ring-major. */
+int fbr_sc_describe(fbr_ctx* ctx, const fbr_sc_params* sp, const fbr_point_xyzi* corner, int64_t n_corner,
+                    const fbr_point_xyzi* surf, int64_t n_surf, float* desc_out);
+/* Describes the keyframes added since the last call (one launch for all of them); *n_described
+ * (optional) = how many.  A descriptor depends only on the lidar-frame cloud: fbr_keyframes_set_pose
+ * invalidates nothing.  fbr_keyframes_reset, or a call with another n_ring, n_sector, max_radius or
+ * lidar_height, discards the store (the next update describes every keyframe).  The query and loop
+ * calls below run it themselves. */
+int fbr_sc_update(fbr_ctx* ctx, const fbr_sc_params* sp, int64_t* n_described);
+/* Diagnostic: the stored descriptor of one keyframe (shape: the last fbr_sc_update's).
+ * FBR_ERR_STATE when that keyframe has not been described yet. */
+int fbr_sc_descriptor(fbr_ctx* ctx, int64_t keyframe, float* desc_out);
+/* The query cloud in the form the keyframes hold: mapping-leaf down-sampled corner and surf features
+ * in the lidar frame.  Searches every keyframe; out[0 .. *n_out) = the min(k, N) best matches in
+ * rank order, whatever their distance (dist_threshold is not applied); *n_out = 0 without keyframes.
+ * 1 <= k <= FBR_SC_MAX_K.  Invalid parameters: FBR_ERR_INVALID_ARG before anything is enqueued.  One
+ * device-to-host copy (the N candidate records); the host never touches a descriptor. */
+int fbr_sc_query(fbr_ctx* ctx, const fbr_sc_params* sp, const fbr_point_xyzi* corner, int64_t n_corner,
+                 const fbr_point_xyzi* surf, int64_t n_surf, int k, fbr_sc_match* out, int* n_out);
+/* detectLoopClosure by appearance: the query is the last keyframe's stored descriptor, the
+ * candidates every other keyframe with |time - stamp| > lp->search_time_diff (fbr_detect_loop_closure's
+ * expression).  The best candidate is returned if its distance is below dist_threshold; otherwise
+ * both ids are -1 (FBR_OK).  *match (optional) = the best candidate either way (keyframe -1 and
+ * zeros when there is no candidate at all). */
+int fbr_sc_detect_loop_closure(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, const fbr_sc_params* sp,
+                               int32_t* latest_id, int32_t* closest_id, fbr_sc_match* match);
+/* fbr_perform_loop_closure with two substitutions for this call only: the candidate comes from
+ * fbr_sc_detect_loop_closure, and match.pose_guess stands for the stored pose of the last keyframe
+ * wherever performLoopClosure reads it (the source cloud's transform, tWrong, and through them
+ * pose_corrected and between).  Every other step, field and status is fbr_perform_loop_closure's (a
+ * target range closest +- search_num that reaches the last keyframe itself takes it at its stored
+ * pose).  No key pose is changed; the registration map, its grids and a keyframe local map are not
+ * touched. */
+int fbr_perform_loop_closure_sc(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, const fbr_sc_params* sp,
+                                fbr_loop_result* out, fbr_sc_match* match);
+
 /* Down-sampled global map actually used (sizes, then optional copies; pass NULL to skip).  After
  * fbr_extract_surrounding_keyframes: the keyframe local map (laserCloud{Corner,Surf}FromMapDS). */
 int fbr_get_map(fbr_ctx* ctx, int64_t* n_corner, int64_t* n_surf, fbr_point_xyzi* corner,

@@ -313,6 +313,55 @@ class MapOptimization {
     return r;
   }
 
+  /* Place recognition (include/fbr.h, "place recognition"): scan-context descriptors of the
+   * keyframes and the exhaustive search over them.  scQuery takes mapping-leaf down-sampled lidar-frame
+   * features and returns up to k pose hypotheses in rank order, each to be tried with registration();
+   * the *SC loop calls find the revisited place by appearance, so they still work once the drift of
+   * the last key pose exceeds historyKeyframeSearchRadius. */
+  std::vector<float> scDescribe(const fbr_sc_params& sp, const std::vector<fbr_point_xyzi>& corner,
+                                const std::vector<fbr_point_xyzi>& surf) {
+    std::vector<float> d((size_t)sp.n_ring * (size_t)sp.n_sector);
+    check(fbr_sc_describe(c_.get(), &sp, corner.data(), (int64_t)corner.size(), surf.data(), (int64_t)surf.size(), d.data()),
+          "fbr_sc_describe");
+    return d;
+  }
+  int64_t scUpdate(const fbr_sc_params& sp) {
+    int64_t n = 0;
+    check(fbr_sc_update(c_.get(), &sp, &n), "fbr_sc_update");
+    return n;
+  }
+  std::vector<float> scDescriptor(const fbr_sc_params& sp, int64_t keyframe) {
+    std::vector<float> d((size_t)sp.n_ring * (size_t)sp.n_sector);
+    check(fbr_sc_descriptor(c_.get(), keyframe, d.data()), "fbr_sc_descriptor");
+    return d;
+  }
+  std::vector<fbr_sc_match> scQuery(const fbr_sc_params& sp, const std::vector<fbr_point_xyzi>& corner,
+                                    const std::vector<fbr_point_xyzi>& surf, int k) {
+    std::vector<fbr_sc_match> m((size_t)(k > 0 ? k : 1));
+    int n = 0;
+    check(fbr_sc_query(c_.get(), &sp, corner.data(), (int64_t)corner.size(), surf.data(), (int64_t)surf.size(), k, m.data(),
+                       &n),
+          "fbr_sc_query");
+    m.resize((size_t)n);
+    return m;
+  }
+  bool detectLoopClosureSC(double timeLaserCloudInfoLast, const fbr_loop_params& lp, const fbr_sc_params& sp, int* latestID,
+                           int* closestID, fbr_sc_match* match = nullptr) {
+    int32_t a = -1, b = -1;
+    check(fbr_sc_detect_loop_closure(c_.get(), timeLaserCloudInfoLast, &lp, &sp, &a, &b, match),
+          "fbr_sc_detect_loop_closure");
+    if (latestID) *latestID = a;
+    if (closestID) *closestID = b;
+    return a >= 0;
+  }
+  fbr_loop_result performLoopClosureSC(double timeLaserCloudInfoLast, const fbr_loop_params& lp, const fbr_sc_params& sp,
+                                       fbr_sc_match* match = nullptr) {
+    fbr_loop_result r{};
+    check(fbr_perform_loop_closure_sc(c_.get(), timeLaserCloudInfoLast, &lp, &sp, &r, match),
+          "fbr_perform_loop_closure_sc");
+    return r;
+  }
+
  private:
   Context& c_;
   double timeLastProcessing_ = -1.0;  // mapOptmization.h:135 (timeLastProcessing = -1)
