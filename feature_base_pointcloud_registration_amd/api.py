@@ -16,8 +16,8 @@ import os
 import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
-                        FbrLoopResult, FbrParams, FbrRegStats, FbrScMatch, PointCloud2, default_params, icp_params,
-                        loop_params, ptr, sc_params)
+                        FbrLoopResult, FbrParams, FbrPgResult, FbrRegStats, FbrScMatch, PointCloud2, default_params,
+                        icp_params, loop_params, pg_params, ptr, sc_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align", "fbr_selftest_nn1",
     "fbr_sc_params_default", "fbr_sc_describe", "fbr_sc_update", "fbr_sc_descriptor", "fbr_sc_query",
     "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
+    "fbr_pg_params_default", "fbr_pg_reset", "fbr_pg_add_prior", "fbr_pg_add_between", "fbr_pg_add_between_poses",
+    "fbr_pg_add_gps", "fbr_pg_add_loop", "fbr_pg_factor_count", "fbr_pg_optimize", "fbr_pg_poses", "fbr_pg_apply",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -136,6 +138,17 @@ def lib():
             "fbr_sc_query": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, ctypes.c_int, _VP, _VP]),
             "fbr_sc_detect_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP, _VP, _VP]),
             "fbr_perform_loop_closure_sc": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP, _VP]),
+            "fbr_pg_params_default": (None, [_VP]),
+            "fbr_pg_reset": (ctypes.c_int, [_VP]),
+            "fbr_pg_add_prior": (ctypes.c_int, [_VP, _I64, _VP, _VP]),
+            "fbr_pg_add_between": (ctypes.c_int, [_VP, _I64, _I64, _VP, _VP]),
+            "fbr_pg_add_between_poses": (ctypes.c_int, [_VP, _I64, _I64, _VP, _VP, _VP]),
+            "fbr_pg_add_gps": (ctypes.c_int, [_VP, _I64, _VP, _VP]),
+            "fbr_pg_add_loop": (ctypes.c_int, [_VP, _VP, _VP]),
+            "fbr_pg_factor_count": (ctypes.c_int, [_VP, _VP]),
+            "fbr_pg_optimize": (ctypes.c_int, [_VP, _VP, _VP]),
+            "fbr_pg_poses": (ctypes.c_int, [_VP, _VP, _I64, _VP]),
+            "fbr_pg_apply": (ctypes.c_int, [_VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
             "fbr_comm_create_local": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int]),
@@ -638,6 +651,70 @@ class Context:
         _check(lib().fbr_perform_loop_closure_sc(self._h, ctypes.c_double(stamp), ctypes.byref(lp), ctypes.byref(sp),
                                                  ctypes.byref(r), ctypes.byref(m)), "fbr_perform_loop_closure_sc")
         return (r, m) if raw else (r.as_dict(), None if m.keyframe < 0 else m.as_dict())
+
+    # ---- pose graph (include/fbr.h "pose graph") ----
+    def pg_reset(self):
+        _check(lib().fbr_pg_reset(self._h), "fbr_pg_reset")
+
+    def pg_add_prior(self, node, pose, variances):
+        """PriorFactor<Pose3> on keyframe `node`: pose [roll, pitch, yaw, x, y, z], variances [6] in
+        the same order."""
+        p, v = np.ascontiguousarray(pose, np.float32), np.ascontiguousarray(variances, np.float64)
+        assert p.shape == (6,) and v.shape == (6,)
+        _check(lib().fbr_pg_add_prior(self._h, int(node), ptr(p), ptr(v)), "fbr_pg_add_prior")
+
+    def pg_add_between(self, i, j, between, variances):
+        """BetweenFactor<Pose3>(i, j) with the measured T_i^-1 T_j as a row-major 4x4 float matrix."""
+        m, v = np.ascontiguousarray(between, np.float32).reshape(16), np.ascontiguousarray(variances, np.float64)
+        assert v.shape == (6,)
+        _check(lib().fbr_pg_add_between(self._h, int(i), int(j), ptr(m), ptr(v)), "fbr_pg_add_between")
+
+    def pg_add_between_poses(self, i, j, pose_i, pose_j, variances):
+        """BetweenFactor<Pose3>(i, j, pose_i.between(pose_j)): how odometry is added (:1533-1537)."""
+        a, b = np.ascontiguousarray(pose_i, np.float32), np.ascontiguousarray(pose_j, np.float32)
+        v = np.ascontiguousarray(variances, np.float64)
+        assert a.shape == (6,) and b.shape == (6,) and v.shape == (6,)
+        _check(lib().fbr_pg_add_between_poses(self._h, int(i), int(j), ptr(a), ptr(b), ptr(v)), "fbr_pg_add_between_poses")
+
+    def pg_add_gps(self, node, xyz, variances):
+        p, v = np.ascontiguousarray(xyz, np.float64), np.ascontiguousarray(variances, np.float64)
+        assert p.shape == (3,) and v.shape == (3,)
+        _check(lib().fbr_pg_add_gps(self._h, int(node), ptr(p), ptr(v)), "fbr_pg_add_gps")
+
+    def pg_add_loop(self, loop_result):
+        """The between factor of a closed loop (perform_loop_closure(..., raw=True)'s FbrLoopResult);
+        returns whether one was added (status FBR_LOOP_CLOSED)."""
+        added = ctypes.c_int()
+        _check(lib().fbr_pg_add_loop(self._h, ctypes.byref(loop_result), ctypes.byref(added)), "fbr_pg_add_loop")
+        return bool(added.value)
+
+    def pg_factor_count(self):
+        n = _I64()
+        _check(lib().fbr_pg_factor_count(self._h, ctypes.byref(n)), "fbr_pg_factor_count")
+        return n.value
+
+    def pg_poses(self):
+        """The last optimise's poses: float64 [N, 6] = [roll, pitch, yaw, x, y, z]."""
+        n = _I64()
+        rc = lib().fbr_pg_poses(self._h, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):  # FBR_ERR_CAPACITY: the count is in n
+            _check(rc, "fbr_pg_poses")
+        out = np.zeros((max(n.value, 1), 6), np.float64)
+        _check(lib().fbr_pg_poses(self._h, ptr(out), len(out), ctypes.byref(n)), "fbr_pg_poses")
+        return out[:n.value]
+
+    def pg_optimize(self, params=None, raw=False):
+        """Optimise the key poses under the factors: (poses float64 [N, 6], fbr_pg_result as a dict;
+        raw: the FbrPgResult itself).  No key pose changes until pg_apply."""
+        p = params if params is not None else pg_params()
+        r = FbrPgResult()
+        _check(lib().fbr_pg_optimize(self._h, ctypes.byref(p), ctypes.byref(r)), "fbr_pg_optimize")
+        poses = self.pg_poses() if r.n_nodes > 0 else np.zeros((0, 6), np.float64)
+        return poses, (r if raw else r.as_dict())
+
+    def pg_apply(self):
+        """correctPoses: the optimised poses, rounded to float, become the key poses."""
+        _check(lib().fbr_pg_apply(self._h), "fbr_pg_apply")
 
     def relocalize(self, points, k=4, sc=None):
         """Find the pose of one raw scan (POINT_XYZIRT) without a guess: project, extract features,

@@ -9,6 +9,7 @@
 //   fbr_map.hip     map VoxelGrid and kNN grids, keyframe store and local map, pose helpers
 //   fbr_loop.hip    loop closure candidate search and ICP
 //   fbr_sc.hip      scan-context place recognition: descriptor store, search, loop closure under drift
+//   fbr_pg.hip      pose graph: the factor list, the Levenberg-Marquardt driver, correctPoses
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -457,6 +458,20 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   Dev<uint32_t> d_sc_q;           // the query slot: one descriptor of the largest shape
   Dev<double> d_sc_qn;            // ... and its column norms
   GrowDev<float4> d_sc_cloud;     // an uploaded query cloud, corner then surf
+
+  // ---- pose graph (fbr_pg.hip) ----
+  // The factors live on the host, like kf_poses, and are uploaded per optimise; fbr_keyframes_reset
+  // (fbr_map.hip) empties them.  Every buffer is allocated on first use and grown on demand.
+  std::vector<PgFactor> pg_factors;
+  std::vector<double> pg_result;   // [pg_result_n][6] the last optimise's poses
+  int64_t pg_result_n = -1;        // the store's size at that optimise (-1: no result)
+  GrowDev<PgFactor> d_pg_fac;
+  GrowDev<int32_t> d_pg_adj;       // the two adjacency lists: offsets, then entries
+  GrowDev<double> d_pg_work;       // every double array of an optimise (fbr_pg.hip pg_prepare)
+  Dev<PgState> d_pg_state;
+  Mapped<unsigned long long> h_pg_flag;     // host-mapped progress word, written by k_pg_decide
+  unsigned long long* d_pg_flag = nullptr;  // not owning: h_pg_flag's device address
+  unsigned long long pg_gen = 0;
 
   // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;

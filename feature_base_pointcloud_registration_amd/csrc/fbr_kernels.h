@@ -8,6 +8,7 @@
 #include <atomic>
 
 #include "fbr_common.h"
+#include "fbr_pg.h"
 
 namespace fbr {
 
@@ -452,5 +453,42 @@ void launch_sc_norms(hipStream_t s, const uint32_t* desc, int64_t nslots, int n_
 // rec[i] = the match of the query against stored descriptor i, i < n
 void launch_sc_search(hipStream_t s, const uint32_t* qdesc, const double* qnorm, const uint32_t* desc, const double* norms,
                       int64_t n, int n_ring, int n_sector, ScRec* rec);
+
+// ---- pose graph (k_posegraph.hip; the arithmetic is fbr_pg.h's) ----
+struct PgState {
+  double cost[2];      // F of the linearised poses / of the trial poses
+  double rz[2];        // r^T M^-1 r of PCG iteration it (index it & 1) and of the next
+  double rz0, pq, alpha, beta;
+  int32_t stopped;     // the PCG has ended: iteration kernels already enqueued return at once
+  int32_t iters;       // PCG iterations of this solve
+  int32_t numerical;   // a Cholesky pivot was non-positive or non-finite
+  int32_t pad;
+};
+constexpr int kPgMaxLevels = 34;
+struct PgArgs {
+  int64_t n, nf;       // nodes, factors
+  const PgFactor* fac;
+  const int32_t *adj_off, *adj;    // [n + 1], every factor a node touches (factor * 2 + side), factor order
+  const int32_t *ladj_off, *ladj;  // the same of the loop factors alone
+  double* lin;         // [nf][kPgLin]
+  double* fcost;       // [nf] a factor's 1/2 |r|^2
+  double* D0;          // [36][n] T's diagonal blocks without damping
+  double *hd, *g;      // [6][n] diag(H), J^T r
+  double *x, *r, *p, *q;  // [6][n] PCG vectors (z is level 0's x, the solve's right-hand side level 0's b)
+  double* partial;     // [ceil(max(n, nf) / 256)] workgroup partial sums
+  PgState* st;
+  unsigned long long* flag;  // host-mapped: (generation << 32) | iterations << 1 | stopped
+  int nlev;
+  PgLevel lev[kPgMaxLevels];
+};
+// residuals (jac: and Jacobians) of the factors at poses X [n][12]; the cost into st->cost[slot]
+void launch_pg_linearize(hipStream_t s, const PgArgs& a, const double* X, int jac, int slot);
+void launch_pg_assemble(hipStream_t s, const PgArgs& a);
+// level 0's D = D0 + lambda diag(hd), then the cyclic-reduction factor of every level
+void launch_pg_factor(hipStream_t s, const PgArgs& a, double lambda);
+// x = 0, r = -g, z = M^-1 r, p = z
+void launch_pg_pcg_init(hipStream_t s, const PgArgs& a, unsigned long long gen);
+void launch_pg_pcg_iter(hipStream_t s, const PgArgs& a, int it, int max_it, double tol2, unsigned long long gen);
+void launch_pg_retract(hipStream_t s, const PgArgs& a, const double* X, double* Xt);
 
 }  // namespace fbr

@@ -289,6 +289,8 @@ int fbr_keyframes_reset(fbr_ctx* c) {
   c->kf_s_cnt.clear();
   c->kf_c_used = c->kf_s_used = 0;
   c->sc_n = 0;  // the scan-context descriptors go with their keyframes (fbr_sc.hip)
+  c->pg_factors.clear();  // ... and so do the pose graph's factors and its result (fbr_pg.hip)
+  c->pg_result_n = -1;
   return FBR_OK;
 }
 

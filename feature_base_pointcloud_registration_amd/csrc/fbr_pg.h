@@ -1,0 +1,608 @@
+// fbr_pg.h — the pose-graph arithmetic of include/fbr.h ("pose graph"), host and device, all in
+// double: Exp / Log / Jr^-1 of SO(3), the residual and Jacobians of a factor, the 6x6 Cholesky, one
+// level step of the block cyclic reduction with its index arithmetic, and the Euler conversion.
+// k_posegraph.hip compiles these functions for the device and tests/native/pg_probe.cpp for the CPU,
+// so the tests check the kernels' arithmetic without a GPU.  The contract is the project's own
+// restatement of a pose-graph optimiser in GTSAM 4.0's default Pose3 chart; it is pinned by the
+// NumPy model tests/pg_model.py, not against GTSAM.
+//
+// Must be compiled with -ffp-contract=off, as everything here.
+//
+// Every loop below has constant bounds and is unrolled, so the small local arrays stay in registers
+// on the device (a runtime-indexed local array would go to scratch).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+// Free of HIP headers under a plain host compiler, so that a stand-alone CPU program (sanitizers)
+// can include it.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PG_HD __host__ __device__ inline
+#else
+#define PG_HD inline
+#endif
+
+namespace fbr {
+
+enum { kPgPrior = 0, kPgBetween = 1, kPgGps = 2 };
+
+struct PgFactor {
+  int32_t type;  // kPg*
+  int32_t i, j;  // nodes (j = -1 for prior and gps)
+  int32_t loop;  // 1: a between factor with |i - j| != 1, a term of L; 0: a term of T
+  double Z[12];  // the measurement: R row-major [9], t [3] (gps: t only)
+  double w[6];   // 1 / sqrt(variance), tangent order [rotation; translation] (gps: w[0..2] = 0)
+};
+
+constexpr int kPgLin = 78;  // doubles of a linearised factor: r[6], J_i[36], J_j[36] (whitened, row-major)
+
+// ---- 3x3 helpers (row-major) ----
+PG_HD void pg_mul33(const double* A, const double* B, double* C) {  // C = A B
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) C[3 * r + c] = (A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c]) + A[3 * r + 2] * B[6 + c];
+}
+PG_HD void pg_mul33_tn(const double* A, const double* B, double* C) {  // C = A^T B
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) C[3 * r + c] = (A[r] * B[c] + A[3 + r] * B[3 + c]) + A[6 + r] * B[6 + c];
+}
+PG_HD void pg_mulv3(const double* A, const double* v, double* o) {  // o = A v
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[r] = (A[3 * r] * v[0] + A[3 * r + 1] * v[1]) + A[3 * r + 2] * v[2];
+}
+PG_HD void pg_mulv3_t(const double* A, const double* v, double* o) {  // o = A^T v
+#pragma unroll
+  for (int r = 0; r < 3; ++r) o[r] = (A[r] * v[0] + A[3 + r] * v[1]) + A[6 + r] * v[2];
+}
+// I a + K b + K^2 c with K = [w]x (K^2 = w w^T - |w|^2 I)
+PG_HD void pg_rodrigues(const double* w, double a, double b, double c, double* R) {
+  const double x = w[0], y = w[1], z = w[2], t2 = (x * x + y * y) + z * z;
+  R[0] = a + c * (x * x - t2); R[1] = c * (x * y) - b * z;   R[2] = c * (x * z) + b * y;
+  R[3] = c * (x * y) + b * z;   R[4] = a + c * (y * y - t2); R[5] = c * (y * z) - b * x;
+  R[6] = c * (x * z) - b * y;   R[7] = c * (y * z) + b * x;   R[8] = a + c * (z * z - t2);
+}
+
+// Exp of so(3): I + (sin t / t) K + ((1 - cos t) / t^2) K^2, the series below t^2 = 1e-12.
+PG_HD void pg_exp(const double* w, double* R) {
+  const double t2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2];
+  double a, b;
+  if (t2 < 1e-12) {
+    a = 1.0 - t2 / 6.0;
+    b = 0.5 - t2 / 24.0;
+  } else {
+    const double t = sqrt(t2);
+    a = sin(t) / t;
+    b = (1.0 - cos(t)) / t2;
+  }
+  pg_rodrigues(w, 1.0, a, b, R);
+}
+
+// Log of SO(3).  v = vee(R - R^T) = 2 sin t * axis, c = (trace - 1) / 2, t = atan2(|v| / 2, c).
+//   t^2 < 1e-12:  w = v / 2 * (1 + t^2 / 6)
+//   c > -0.99:    w = v / 2 * t / sin t
+//   otherwise (t near pi, sin t small): the axis from the symmetric part, (R + R^T) / 2 = c I +
+//     (1 - c) a a^T: the largest a_p^2 = (R_pp - c) / (1 - c) gives a_p, the others follow from row
+//     p; its sign is v's (either at t = pi exactly).  No branch divides by a vanishing quantity.
+PG_HD void pg_log(const double* R, double* w) {
+  const double v[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+  double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+  c = c > 1.0 ? 1.0 : c < -1.0 ? -1.0 : c;
+  const double s = 0.5 * sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+  const double t = atan2(s, c);
+  if (t * t < 1e-12) {
+    const double k = 0.5 * (1.0 + t * t / 6.0);
+    w[0] = k * v[0]; w[1] = k * v[1]; w[2] = k * v[2];
+  } else if (c > -0.99) {
+    const double k = 0.5 * t / s;
+    w[0] = k * v[0]; w[1] = k * v[1]; w[2] = k * v[2];
+  } else {
+    const double d0 = R[0], d1 = R[4], d2 = R[8], omc = 1.0 - c;
+    double a[3];
+    if (d0 >= d1 && d0 >= d2) {
+      a[0] = sqrt((d0 - c) / omc);
+      a[1] = (R[1] + R[3]) / (2.0 * omc * a[0]);
+      a[2] = (R[2] + R[6]) / (2.0 * omc * a[0]);
+    } else if (d1 >= d2) {
+      a[1] = sqrt((d1 - c) / omc);
+      a[0] = (R[1] + R[3]) / (2.0 * omc * a[1]);
+      a[2] = (R[5] + R[7]) / (2.0 * omc * a[1]);
+    } else {
+      a[2] = sqrt((d2 - c) / omc);
+      a[0] = (R[2] + R[6]) / (2.0 * omc * a[2]);
+      a[1] = (R[5] + R[7]) / (2.0 * omc * a[2]);
+    }
+    const double n = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+    const double sg = ((a[0] * v[0] + a[1] * v[1]) + a[2] * v[2]) < 0.0 ? -1.0 : 1.0;
+    const double k = sg * t / n;
+    w[0] = k * a[0]; w[1] = k * a[1]; w[2] = k * a[2];
+  }
+}
+
+// Jr^-1(phi) = I + K / 2 + (1 / t^2 - cot(t / 2) / (2 t)) K^2, which is the contract's
+// 1 / t^2 - (1 + cos t) / (2 t sin t) without its 0 / 0 at t = pi; 1 / 12 + t^2 / 720 below t^2 = 1e-6.
+PG_HD void pg_jrinv(const double* phi, double* J) {
+  const double t2 = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
+  double k;
+  if (t2 < 1e-6) {
+    k = 1.0 / 12.0 + t2 / 720.0;
+  } else {
+    const double t = sqrt(t2), h = 0.5 * t;
+    k = 1.0 / t2 - (cos(h) / sin(h)) / (2.0 * t);
+  }
+  pg_rodrigues(phi, 1.0, 0.5, k, J);
+}
+
+// Pose [12] = R row-major [9], t [3], from [roll, pitch, yaw, x, y, z]: R = Rz(yaw) Ry(pitch) Rx(roll).
+PG_HD void pg_pose_from_euler(const double* e, double* X) {
+  const double cr = cos(e[0]), sr = sin(e[0]), cp = cos(e[1]), sp = sin(e[1]), cy = cos(e[2]), sy = sin(e[2]);
+  X[0] = cy * cp; X[1] = cy * sp * sr - sy * cr; X[2] = cy * sp * cr + sy * sr;
+  X[3] = sy * cp; X[4] = sy * sp * sr + cy * cr; X[5] = sy * sp * cr - cy * sr;
+  X[6] = -sp;     X[7] = cp * sr;                X[8] = cp * cr;
+  X[9] = e[3]; X[10] = e[4]; X[11] = e[5];
+}
+// roll = atan2(R21, R22), pitch = asin(-R20) clamped, yaw = atan2(R10, R00)
+PG_HD void pg_euler_from_pose(const double* X, double* e) {
+  double s = -X[6];
+  s = s > 1.0 ? 1.0 : s < -1.0 ? -1.0 : s;
+  e[0] = atan2(X[7], X[8]);
+  e[1] = asin(s);
+  e[2] = atan2(X[3], X[0]);
+  e[3] = X[9]; e[4] = X[10]; e[5] = X[11];
+}
+// A^-1 B of two poses
+PG_HD void pg_between(const double* A, const double* B, double* D) {
+  pg_mul33_tn(A, B, D);
+  const double dt[3] = {B[9] - A[9], B[10] - A[10], B[11] - A[11]};
+  pg_mulv3_t(A, dt, D + 9);
+}
+// T (+) [w; v] = (R Exp(w), t + R v)
+PG_HD void pg_retract(const double* X, const double* d, double* Y) {
+  double E[9], rv[3];
+  pg_exp(d, E);
+  pg_mul33(X, E, Y);
+  pg_mulv3(X, d + 3, rv);
+  Y[9] = X[9] + rv[0]; Y[10] = X[10] + rv[1]; Y[11] = X[11] + rv[2];
+}
+
+// The whitened residual r[6] of a factor and, with jac, its whitened Jacobians Ji, Jj [36]
+// (row-major, tangent order [rotation; translation]; Jj is zero for prior and gps).  Xj is not read
+// for prior and gps.  Derivation: include/fbr.h "pose graph".
+PG_HD void pg_factor_eval(const PgFactor& f, const double* Xi, const double* Xj, bool jac, double* r, double* Ji,
+                          double* Jj) {
+  if (jac) {
+#pragma unroll
+    for (int k = 0; k < 36; ++k) Ji[k] = Jj[k] = 0.0;
+  }
+  if (f.type == kPgGps) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      r[k] = 0.0;
+      r[3 + k] = (Xi[9 + k] - f.Z[9 + k]) * f.w[3 + k];
+    }
+    if (jac) {
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) Ji[6 * (3 + a) + 3 + b] = Xi[3 * a + b] * f.w[3 + a];
+    }
+    return;
+  }
+  const bool between = f.type == kPgBetween;
+  double D[12];  // T_i^-1 T_j, or T_i for a prior
+  if (between) {
+    pg_between(Xi, Xj, D);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) D[k] = Xi[k];
+  }
+  double E[9], phi[3], et[3];
+  pg_mul33_tn(f.Z, D, E);  // E_R = Z_R^T D_R
+  pg_log(E, phi);
+  const double dt[3] = {D[9] - f.Z[9], D[10] - f.Z[10], D[11] - f.Z[11]};
+  pg_mulv3_t(f.Z, dt, et);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r[k] = phi[k] * f.w[k];
+    r[3 + k] = et[k] * f.w[3 + k];
+  }
+  if (!jac) return;
+  double Jr[9];
+  pg_jrinv(phi, Jr);
+  double* Jn = between ? Jj : Ji;  // the "j half": d e_rot / d w = Jr^-1, d e_t / d v = E_R
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      Jn[6 * a + b] = Jr[3 * a + b] * f.w[a];
+      Jn[6 * (3 + a) + 3 + b] = E[3 * a + b] * f.w[3 + a];
+    }
+  if (!between) return;
+  // the "i half": d e_rot / d w = -Jr^-1 D_R^T, d e_t / d w = Z_R^T [D_t]x, d e_t / d v = -Z_R^T
+  const double S[9] = {0.0, -D[11], D[10], D[11], 0.0, -D[9], -D[10], D[9], 0.0};
+  double ZS[9];
+  pg_mul33_tn(f.Z, S, ZS);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const double jd = (Jr[3 * a] * D[3 * b] + Jr[3 * a + 1] * D[3 * b + 1]) + Jr[3 * a + 2] * D[3 * b + 2];
+      Ji[6 * a + b] = -jd * f.w[a];
+      Ji[6 * (3 + a) + b] = ZS[3 * a + b] * f.w[3 + a];
+      Ji[6 * (3 + a) + 3 + b] = -f.Z[3 * b + a] * f.w[3 + a];
+    }
+}
+
+// ---- 6x6 Cholesky (row-major, lower): A = L L^T from A's lower triangle ----
+// Returns false on a non-positive or non-finite pivot (the factor is then completed with that
+// pivot taken as 1, so that nothing downstream divides by zero).
+PG_HD bool pg_chol6(const double* A, double* L) {
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = A[6 * j + j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d = d - L[6 * j + k] * L[6 * j + k];
+    if (!(d > 0.0) || !(d < INFINITY)) {
+      ok = false;
+      d = 1.0;
+    }
+    const double l = sqrt(d);
+    L[6 * j + j] = l;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double s = A[6 * i + j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) s = s - L[6 * i + k] * L[6 * j + k];
+      L[6 * i + j] = s / l;
+    }
+#pragma unroll
+    for (int i = 0; i < j; ++i) L[6 * i + j] = 0.0;
+  }
+  return ok;
+}
+// x = (L L^T)^-1 b, in place
+PG_HD void pg_chol6_solve(const double* L, double* x) {
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double s = x[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) s = s - L[6 * i + k] * x[k];
+    x[i] = s / L[6 * i + i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double s = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) s = s - L[6 * k + i] * x[k];
+    x[i] = s / L[6 * i + i];
+  }
+}
+
+// ---- block cyclic reduction of a symmetric positive definite block-tridiagonal system ----
+// A level holds n nodes: node m's diagonal block D[m] and its coupling A[m] = T[m][m-1] to the node
+// before it (A[0] unused), its right-hand side b[m] and solution x[m].  Arrays are
+// structure-of-arrays: entry e of node m is X[e * n + m] (consecutive threads, consecutive
+// addresses).  The odd nodes of a level are eliminated; the even node m = 2q becomes node q of the
+// next level, which has (n + 1) / 2 nodes; the last level has one node.
+//
+// Factor, per level:
+//   pg_cr_elim(k), k odd (or the single node of the last level): L[k] = chol(D[k]),
+//     G[k] = D[k]^-1 A[k], H[k] = D[k]^-1 A[k+1]^T (zero when k + 1 == n)
+//   pg_cr_update(q): next.D[q] = D[m] - A[m] H[m-1] - A[m+1]^T G[m+1],
+//                    next.A[q] = -A[m] G[m-1]            (terms of absent neighbours dropped)
+// Solve, per level down, then the last level's node, then per level up:
+//   pg_cr_reduce(q):  next.b[q] = b[m] - H[m-1]^T b[m-1] - G[m+1]^T b[m+1]
+//   pg_cr_top():      x[0] = D[0]^-1 b[0]
+//   pg_cr_backsub(m): x[m] = next.x[m / 2] (m even);
+//                     x[m] = D[m]^-1 b[m] - G[m] x[m-1] - H[m] x[m+1] (m odd, x[m+-1] from next.x)
+// Each step reads only what earlier steps wrote: a level step is one kernel (or one loop on the CPU).
+struct PgLevel {
+  int64_t n;
+  double *D, *A, *L, *G, *H;  // [36][n]
+  double *b, *x;              // [6][n]
+};
+
+PG_HD void pg_ld36(const double* X, int64_t n, int64_t m, double* M) {
+#pragma unroll
+  for (int e = 0; e < 36; ++e) M[e] = X[e * n + m];
+}
+PG_HD void pg_st36(double* X, int64_t n, int64_t m, const double* M) {
+#pragma unroll
+  for (int e = 0; e < 36; ++e) X[e * n + m] = M[e];
+}
+PG_HD void pg_ld6(const double* X, int64_t n, int64_t m, double* v) {
+#pragma unroll
+  for (int e = 0; e < 6; ++e) v[e] = X[e * n + m];
+}
+PG_HD void pg_st6(double* X, int64_t n, int64_t m, const double* v) {
+#pragma unroll
+  for (int e = 0; e < 6; ++e) X[e * n + m] = v[e];
+}
+
+PG_HD bool pg_cr_is_elim(int64_t n, int64_t k) { return (k & 1) || n == 1; }
+
+// false: a bad pivot
+PG_HD bool pg_cr_elim(const PgLevel& lv, int64_t k) {
+  const int64_t n = lv.n;
+  double M[36], L[36];
+  pg_ld36(lv.D, n, k, M);
+  const bool ok = pg_chol6(M, L);
+  pg_st36(lv.L, n, k, L);
+  // column by column: G[:, c] = D^-1 A[k][:, c], H[:, c] = D^-1 A[k+1][c, :]^T
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double g[6], h[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      g[r] = k >= 1 ? lv.A[(6 * r + c) * n + k] : 0.0;
+      h[r] = k + 1 < n ? lv.A[(6 * c + r) * n + k + 1] : 0.0;
+    }
+    pg_chol6_solve(L, g);
+    pg_chol6_solve(L, h);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      lv.G[(6 * r + c) * n + k] = g[r];
+      lv.H[(6 * r + c) * n + k] = h[r];
+    }
+  }
+  return ok;
+}
+
+PG_HD void pg_cr_update(const PgLevel& lv, const PgLevel& nx, int64_t q) {
+  const int64_t n = lv.n, m = 2 * q;
+  double Dn[36], An[36];
+  pg_ld36(lv.D, n, m, Dn);
+#pragma unroll
+  for (int e = 0; e < 36; ++e) An[e] = 0.0;
+  if (m >= 1) {
+    double Am[36], X[36];
+    pg_ld36(lv.A, n, m, Am);
+    pg_ld36(lv.H, n, m - 1, X);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = s + Am[6 * r + k] * X[6 * k + c];
+        Dn[6 * r + c] = Dn[6 * r + c] - s;
+      }
+    pg_ld36(lv.G, n, m - 1, X);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = s + Am[6 * r + k] * X[6 * k + c];
+        An[6 * r + c] = -s;
+      }
+  }
+  if (m + 1 < n) {
+    double Ap[36], X[36];
+    pg_ld36(lv.A, n, m + 1, Ap);
+    pg_ld36(lv.G, n, m + 1, X);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = s + Ap[6 * k + r] * X[6 * k + c];
+        Dn[6 * r + c] = Dn[6 * r + c] - s;
+      }
+  }
+  pg_st36(nx.D, nx.n, q, Dn);
+  pg_st36(nx.A, nx.n, q, An);
+}
+
+PG_HD void pg_cr_reduce(const PgLevel& lv, const PgLevel& nx, int64_t q) {
+  const int64_t n = lv.n, m = 2 * q;
+  double b[6], v[6];
+  pg_ld6(lv.b, n, m, b);
+  if (m >= 1) {
+    pg_ld6(lv.b, n, m - 1, v);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + lv.H[(6 * k + c) * n + m - 1] * v[k];
+      b[c] = b[c] - s;
+    }
+  }
+  if (m + 1 < n) {
+    pg_ld6(lv.b, n, m + 1, v);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + lv.G[(6 * k + c) * n + m + 1] * v[k];
+      b[c] = b[c] - s;
+    }
+  }
+  pg_st6(nx.b, nx.n, q, b);
+}
+
+PG_HD void pg_cr_top(const PgLevel& lv) {
+  double L[36], x[6];
+  pg_ld36(lv.L, lv.n, 0, L);
+  pg_ld6(lv.b, lv.n, 0, x);
+  pg_chol6_solve(L, x);
+  pg_st6(lv.x, lv.n, 0, x);
+}
+
+PG_HD void pg_cr_backsub(const PgLevel& lv, const PgLevel& nx, int64_t m) {
+  const int64_t n = lv.n;
+  double x[6];
+  if (!(m & 1)) {
+    pg_ld6(nx.x, nx.n, m >> 1, x);
+    pg_st6(lv.x, n, m, x);
+    return;
+  }
+  double L[36], v[6];
+  pg_ld36(lv.L, n, m, L);
+  pg_ld6(lv.b, n, m, x);
+  pg_chol6_solve(L, x);
+  pg_ld6(nx.x, nx.n, (m - 1) >> 1, v);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s = s + lv.G[(6 * r + k) * n + m] * v[k];
+    x[r] = x[r] - s;
+  }
+  if (m + 1 < n) {
+    pg_ld6(nx.x, nx.n, (m + 1) >> 1, v);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + lv.H[(6 * r + k) * n + m] * v[k];
+      x[r] = x[r] - s;
+    }
+  }
+  pg_st6(lv.x, n, m, x);
+}
+
+// Levels of an n-node system and their total node count (the arrays' extent in nodes).
+PG_HD int pg_cr_levels(int64_t n, int64_t* total) {
+  int levels = 1;
+  int64_t t = n;
+  while (n > 1) {
+    n = (n + 1) / 2;
+    t += n;
+    ++levels;
+  }
+  if (total) *total = t;
+  return levels;
+}
+
+// ---- per-node assembly and products (gathers in adjacency order; no atomics) ----
+// adjacency entry = factor * 2 + side (side 0: the node is the factor's i, 1: its j)
+
+// Node m's rows of the undamped T (diagonal block D0, coupling A = T[m][m-1]), of g = J^T r and of
+// diag(H) (hd, the loop factors included), from the linearised factors in adjacency order.
+PG_HD void pg_assemble_node(int64_t n, int64_t m, const PgFactor* fac, const double* lin, const int32_t* adj_off,
+                            const int32_t* adj, double* D0, double* A, double* g, double* hd) {
+  double D[36], C[36], gv[6], hv[6];
+#pragma unroll
+  for (int e = 0; e < 36; ++e) D[e] = C[e] = 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) gv[e] = hv[e] = 0.0;
+  for (int32_t a = adj_off[m]; a < adj_off[m + 1]; ++a) {
+    const int32_t k = adj[a] >> 1, side = adj[a] & 1;
+    const double* r = lin + (int64_t)k * kPgLin;
+    const double* Js = r + 6 + 36 * side;
+    const double* Jo = r + 6 + 36 * (1 - side);
+    const int32_t loop = fac[k].loop, other = side ? fac[k].i : fac[k].j;
+    const bool band = !loop && fac[k].type == kPgBetween && (int64_t)other == m - 1;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0, d = 0.0;
+#pragma unroll
+      for (int q = 0; q < 6; ++q) {
+        s = s + Js[6 * q + c] * r[q];
+        d = d + Js[6 * q + c] * Js[6 * q + c];
+      }
+      gv[c] = gv[c] + s;
+      hv[c] = hv[c] + d;
+    }
+    if (!loop) {
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          double s = 0.0;
+#pragma unroll
+          for (int q = 0; q < 6; ++q) s = s + Js[6 * q + rr] * Js[6 * q + c];
+          D[6 * rr + c] = D[6 * rr + c] + s;
+        }
+    }
+    if (band) {
+#pragma unroll
+      for (int rr = 0; rr < 6; ++rr)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          double s = 0.0;
+#pragma unroll
+          for (int q = 0; q < 6; ++q) s = s + Js[6 * q + rr] * Jo[6 * q + c];
+          C[6 * rr + c] = C[6 * rr + c] + s;
+        }
+    }
+  }
+  pg_st36(D0, n, m, D);
+  pg_st36(A, n, m, C);
+  pg_st6(g, n, m, gv);
+  pg_st6(hd, n, m, hv);
+}
+
+// Node m's rows of q = H p = T p + L p: the damped diagonal block D, the couplings A, and the loop
+// factors of ladj (J_side^T (J_i p_i + J_j p_j), in adjacency order).  Returns p_m . q_m.
+PG_HD double pg_hp_node(int64_t n, int64_t m, const PgFactor* fac, const double* lin, const int32_t* ladj_off,
+                        const int32_t* ladj, const double* D, const double* A, const double* p, double* q) {
+  double pm[6], v[6], o[6];
+  pg_ld6(p, n, m, pm);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    double s = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s = s + D[(6 * r + k) * n + m] * pm[k];
+    o[r] = s;
+  }
+  if (m >= 1) {
+    pg_ld6(p, n, m - 1, v);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + A[(6 * r + k) * n + m] * v[k];
+      o[r] = o[r] + s;
+    }
+  }
+  if (m + 1 < n) {
+    pg_ld6(p, n, m + 1, v);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + A[(6 * k + r) * n + m + 1] * v[k];
+      o[r] = o[r] + s;
+    }
+  }
+  for (int32_t a = ladj_off[m]; a < ladj_off[m + 1]; ++a) {
+    const int32_t k = ladj[a] >> 1, side = ladj[a] & 1;
+    const double* Ji = lin + (int64_t)k * kPgLin + 6;
+    const double* Jj = Ji + 36;
+    double pi[6], pj[6], u[6];
+    pg_ld6(p, n, fac[k].i, pi);
+    pg_ld6(p, n, fac[k].j, pj);
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s = s + Ji[6 * r + c] * pi[c];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) s = s + Jj[6 * r + c] * pj[c];
+      u[r] = s;
+    }
+    const double* Js = side ? Jj : Ji;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int r = 0; r < 6; ++r) s = s + Js[6 * r + c] * u[r];
+      o[c] = o[c] + s;
+    }
+  }
+  pg_st6(q, n, m, o);
+  double d = 0.0;
+#pragma unroll
+  for (int r = 0; r < 6; ++r) d = d + pm[r] * o[r];
+  return d;
+}
+
+}  // namespace fbr

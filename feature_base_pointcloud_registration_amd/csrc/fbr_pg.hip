@@ -1,0 +1,399 @@
+// fbr_pg.hip — the pose-graph optimiser over the keyframe store (include/fbr.h "pose graph"): the
+// factor list, the Levenberg-Marquardt driver of k_posegraph.hip's kernels, and correctPoses.
+#include "fbr_ctx.h"
+
+namespace {
+
+bool variances_ok(const double* v, int n) {
+  for (int k = 0; k < n; ++k)
+    if (!(v[k] > 0.0) || !(v[k] < INFINITY)) return false;
+  return true;
+}
+bool node_ok(const fbr_ctx* c, int64_t i) { return i >= 0 && i < (int64_t)c->kf_poses.size(); }
+
+void keypose_euler(const fbr_keypose& k, double e[6]) {
+  e[0] = (double)k.roll; e[1] = (double)k.pitch; e[2] = (double)k.yaw;
+  e[3] = (double)k.x; e[4] = (double)k.y; e[5] = (double)k.z;
+}
+
+int add_between(fbr_ctx* c, int64_t i, int64_t j, const double Z[12], const double var[6]) {
+  if (!node_ok(c, i) || !node_ok(c, j) || i == j || !variances_ok(var, 6)) return FBR_ERR_INVALID_ARG;
+  for (int k = 0; k < 12; ++k)
+    if (!std::isfinite(Z[k])) return FBR_ERR_INVALID_ARG;
+  PgFactor f{};
+  f.type = kPgBetween;
+  f.i = (int32_t)i;
+  f.j = (int32_t)j;
+  f.loop = (i - j == 1 || j - i == 1) ? 0 : 1;
+  std::memcpy(f.Z, Z, sizeof(f.Z));
+  for (int k = 0; k < 6; ++k) f.w[k] = 1.0 / std::sqrt(var[k]);
+  c->pg_factors.push_back(f);
+  return FBR_OK;
+}
+
+// The device arrays of one optimise, carved out of c->d_pg_work (doubles) and c->d_pg_adj.
+struct PgPlan {
+  PgArgs a;
+  double *X, *Xt;
+};
+
+int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
+  const std::vector<PgFactor>& F = c->pg_factors;
+  const int64_t nf = (int64_t)F.size();
+  // adjacency in factor order: every factor, and the loop factors alone
+  std::vector<int32_t> adj((size_t)(2 * (n + 1)), 0);
+  int32_t* off = adj.data();
+  int32_t* loff = adj.data() + n + 1;
+  for (const PgFactor& f : F) {
+    ++off[f.i + 1];
+    if (f.j >= 0) ++off[f.j + 1];
+    if (f.loop) {
+      ++loff[f.i + 1];
+      ++loff[f.j + 1];
+    }
+  }
+  for (int64_t m = 0; m < n; ++m) {
+    if (off[m + 1] == 0) return FBR_ERR_STATE;  // a node no factor touches
+    off[m + 1] += off[m];
+    loff[m + 1] += loff[m];
+  }
+  const int64_t na = off[n], nla = loff[n];
+  adj.resize((size_t)(2 * (n + 1) + na + nla));
+  off = adj.data();
+  loff = adj.data() + n + 1;
+  int32_t* ent = adj.data() + 2 * (n + 1);
+  int32_t* lent = ent + na;
+  std::vector<int32_t> cur(off, off + n), lcur(loff, loff + n);
+  for (int64_t k = 0; k < nf; ++k) {
+    const PgFactor& f = F[k];
+    ent[cur[f.i]++] = (int32_t)(2 * k);
+    if (f.j >= 0) ent[cur[f.j]++] = (int32_t)(2 * k + 1);
+    if (f.loop) {
+      lent[lcur[f.i]++] = (int32_t)(2 * k);
+      lent[lcur[f.j]++] = (int32_t)(2 * k + 1);
+    }
+  }
+  int64_t tot = 0;
+  const int nlev = pg_cr_levels(n, &tot);
+  if (nlev > kPgMaxLevels || nf >= ((int64_t)1 << 30) || n >= ((int64_t)1 << 30)) return FBR_ERR_CAPACITY;
+  const int64_t nbmax = (std::max(n, nf) + 255) / 256;
+  const int64_t words = 24 * n + (kPgLin + 1) * nf + 36 * n + 12 * n + 24 * n + nbmax + tot * (36 * 5 + 12);
+  int rc = grow(c->d_pg_work, words, 0, c->stream);
+  if (!rc) rc = grow(c->d_pg_adj, (int64_t)adj.size(), 0, c->stream);
+  if (!rc) rc = grow(c->d_pg_fac, std::max<int64_t>(nf, 1), 0, c->stream);
+  if (rc) return rc;
+  if (!c->d_pg_state && dalloc(c->d_pg_state, 1)) return FBR_ERR_HIP;
+  if (!c->h_pg_flag) {
+    if (dalloc(c->h_pg_flag, 1)) return FBR_ERR_HIP;
+    *c->h_pg_flag = 0;
+    CK(hipHostGetDevicePointer((void**)&c->d_pg_flag, c->h_pg_flag, 0));
+  }
+  CK(hipMemcpyAsync(c->d_pg_adj, adj.data(), sizeof(int32_t) * adj.size(), hipMemcpyHostToDevice, c->stream));
+  CK(hipMemcpyAsync(c->d_pg_fac, F.data(), sizeof(PgFactor) * nf, hipMemcpyHostToDevice, c->stream));
+  CK(hipMemsetAsync(c->d_pg_state, 0, sizeof(PgState), c->stream));
+  CK(fbr_sync(c->stream));  // the pageable copies
+  double* w = c->d_pg_work;
+  auto take = [&w](int64_t count) {
+    double* p = w;
+    w += count;
+    return p;
+  };
+  PgArgs& a = pl->a;
+  a = PgArgs{};
+  a.n = n;
+  a.nf = nf;
+  a.fac = c->d_pg_fac;
+  a.adj_off = c->d_pg_adj;
+  a.ladj_off = c->d_pg_adj + n + 1;
+  a.adj = c->d_pg_adj + 2 * (n + 1);
+  a.ladj = a.adj + na;
+  pl->X = take(12 * n);
+  pl->Xt = take(12 * n);
+  a.lin = take(kPgLin * nf);
+  a.fcost = take(nf);
+  a.D0 = take(36 * n);
+  a.hd = take(6 * n);
+  a.g = take(6 * n);
+  a.x = take(6 * n);
+  a.r = take(6 * n);
+  a.p = take(6 * n);
+  a.q = take(6 * n);
+  a.partial = take(nbmax);
+  a.st = c->d_pg_state;
+  a.flag = c->d_pg_flag;
+  a.nlev = nlev;
+  int64_t ln = n;
+  for (int l = 0; l < nlev; ++l, ln = (ln + 1) / 2) {
+    PgLevel& lv = a.lev[l];
+    lv.n = ln;
+    lv.D = take(36 * ln);
+    lv.A = take(36 * ln);
+    lv.L = take(36 * ln);
+    lv.G = take(36 * ln);
+    lv.H = take(36 * ln);
+    lv.b = take(6 * ln);
+    lv.x = take(6 * ln);
+  }
+  return FBR_OK;
+}
+
+// One damped solve: every iteration is enqueued without waiting; the host only looks at the
+// progress word k_pg_decide writes (and lets the device catch up when it is more than a few
+// iterations behind), and iterations enqueued past the stop return at once.
+void pg_pcg(fbr_ctx* c, const PgArgs& a, const fbr_pg_params& P) {
+  const unsigned long long gen = (++c->pg_gen) & 0xFFFFFFFFull;
+  const volatile unsigned long long* flag = c->h_pg_flag;
+  const double tol2 = P.pcg_rel_tol * P.pcg_rel_tol;
+  constexpr int kLead = 4;  // iterations the host may run ahead of the device
+  TIMED(c, "pg_pcg", launch_pg_pcg_init(c->stream, a, gen));
+  for (int it = 0; it < P.max_pcg_iterations; ++it) {
+    bool stopped = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+      const unsigned long long w = *flag;
+      debug_counters().flag_polls.fetch_add(1, std::memory_order_relaxed);
+      const bool mine = (w >> 32) == gen;
+      stopped = mine && (w & 1);
+      const int seen = mine ? (int)((w & 0xFFFFFFFFull) >> 1) : 0;
+      if (stopped || it - seen <= kLead) break;
+      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;  // enqueue anyway
+    }
+    if (stopped) break;
+    TIMED(c, "pg_pcg", launch_pg_pcg_iter(c->stream, a, it, P.max_pcg_iterations, tol2, gen));
+  }
+}
+
+int pg_read_state(fbr_ctx* c, PgState* st) {
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(st, c->d_pg_state, sizeof(PgState), hipMemcpyDeviceToHost, c->stream));
+  CK(fbr_sync(c->stream));
+  return FBR_OK;
+}
+
+int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
+  const int64_t n = (int64_t)c->kf_poses.size();
+  out->n_nodes = (int32_t)n;
+  out->n_factors = (int32_t)c->pg_factors.size();
+  for (const PgFactor& f : c->pg_factors) out->n_loop_factors += f.loop;
+  out->lambda = P.lambda_init;
+  c->pg_result_n = -1;
+  if (n == 0) {
+    out->status = FBR_PG_EMPTY;
+    return FBR_OK;
+  }
+  PgPlan pl;
+  int rc = pg_prepare(c, n, &pl);
+  if (rc) return rc;
+  const PgArgs& a = pl.a;
+  std::vector<double> X0((size_t)(12 * n)), init((size_t)(6 * n));
+  for (int64_t i = 0; i < n; ++i) {
+    keypose_euler(c->kf_poses[i], &init[6 * i]);
+    pg_pose_from_euler(&init[6 * i], &X0[12 * i]);
+  }
+  double *X = pl.X, *Xt = pl.Xt;
+  CK(hipMemcpyAsync(X, X0.data(), sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->stream));
+  TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, X, 1, 0));
+  TIMED(c, "pg_assemble", launch_pg_assemble(c->stream, a));
+  PgState st;
+  rc = pg_read_state(c, &st);
+  if (rc) return rc;
+  double cost = st.cost[0], lambda = P.lambda_init;
+  out->cost_initial = out->cost_final = cost;
+  int status = -1;
+  if (cost == 0.0) status = FBR_PG_CONVERGED;
+  else if (!(cost < INFINITY)) status = FBR_PG_NUMERICAL;
+  else if (P.max_iterations <= 0) status = FBR_PG_ITERATIONS;
+  while (status < 0) {
+    TIMED(c, "pg_factor", launch_pg_factor(c->stream, a, lambda));
+    pg_pcg(c, a, P);
+    TIMED(c, "pg_retract", launch_pg_retract(c->stream, a, X, Xt));
+    TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, Xt, 0, 1));
+    rc = pg_read_state(c, &st);
+    if (rc) return rc;
+    ++out->trials;
+    out->pcg_iterations += st.iters;
+    if (st.numerical) {
+      status = FBR_PG_NUMERICAL;
+      break;
+    }
+    const double trial = st.cost[1];
+    if (trial < cost) {  // (false for a NaN)
+      std::swap(X, Xt);
+      const double dec = cost - trial, rel = dec / cost;
+      cost = trial;
+      ++out->iterations;
+      lambda /= P.lambda_factor;
+      if (rel < P.rel_cost_tol || dec < P.abs_cost_tol) status = FBR_PG_CONVERGED;
+      else if (out->iterations >= P.max_iterations) status = FBR_PG_ITERATIONS;
+      else {
+        TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, X, 1, 0));
+        TIMED(c, "pg_assemble", launch_pg_assemble(c->stream, a));
+      }
+    } else {
+      lambda *= P.lambda_factor;
+      if (lambda > P.lambda_max) status = FBR_PG_STALLED;
+    }
+  }
+  out->status = status;
+  out->lambda = lambda;
+  c->pg_result.assign((size_t)(6 * n), 0.0);
+  if (status == FBR_PG_NUMERICAL) {  // the optimised poses are the initial ones
+    c->pg_result = init;
+  } else {
+    out->cost_final = cost;
+    CK(hipMemcpyAsync(X0.data(), X, sizeof(double) * 12 * n, hipMemcpyDeviceToHost, c->stream));
+    CK(fbr_sync(c->stream));
+    for (int64_t i = 0; i < n; ++i) {
+      pg_euler_from_pose(&X0[12 * i], &c->pg_result[6 * i]);
+      double A[12], D[12], phi[3];
+      pg_pose_from_euler(&init[6 * i], A);
+      pg_between(A, &X0[12 * i], D);
+      pg_log(D, phi);
+      const double* t = &X0[12 * i + 9];
+      const double dx = t[0] - init[6 * i + 3], dy = t[1] - init[6 * i + 4], dz = t[2] - init[6 * i + 5];
+      out->max_translation_change = std::max(out->max_translation_change, std::sqrt((dx * dx + dy * dy) + dz * dz));
+      out->max_rotation_change =
+          std::max(out->max_rotation_change, std::sqrt((phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2]));
+    }
+  }
+  c->pg_result_n = n;
+  return FBR_OK;
+}
+
+bool pg_params_ok(const fbr_pg_params* p) {
+  return p && p->max_pcg_iterations >= 1 && p->rel_cost_tol >= 0.0 && p->abs_cost_tol >= 0.0 && p->pcg_rel_tol >= 0.0 &&
+         p->lambda_init > 0.0 && p->lambda_init < INFINITY && p->lambda_factor > 1.0 && p->lambda_factor < INFINITY &&
+         p->lambda_max > 0.0;
+}
+
+}  // namespace
+
+extern "C" {
+
+void fbr_pg_params_default(fbr_pg_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->max_iterations = 30;
+  p->max_pcg_iterations = 200;
+  p->rel_cost_tol = 1e-5;  // GTSAM's relativeErrorTol / absoluteErrorTol
+  p->abs_cost_tol = 1e-5;
+  p->pcg_rel_tol = 1e-8;
+  p->lambda_init = 1e-5;
+  p->lambda_factor = 10.0;
+  p->lambda_max = 1e10;
+}
+
+int fbr_pg_reset(fbr_ctx* c) {
+  if (!c) return FBR_ERR_INVALID_ARG;
+  c->pg_factors.clear();
+  return FBR_OK;
+}
+
+int fbr_pg_add_prior(fbr_ctx* c, int64_t node, const float pose[6], const double variances[6]) {
+  if (!c || !pose || !variances || !node_ok(c, node) || !variances_ok(variances, 6)) return FBR_ERR_INVALID_ARG;
+  PgFactor f{};
+  f.type = kPgPrior;
+  f.i = (int32_t)node;
+  f.j = -1;
+  double e[6];
+  for (int k = 0; k < 6; ++k) {
+    if (!std::isfinite(pose[k])) return FBR_ERR_INVALID_ARG;
+    e[k] = (double)pose[k];
+    f.w[k] = 1.0 / std::sqrt(variances[k]);
+  }
+  pg_pose_from_euler(e, f.Z);
+  c->pg_factors.push_back(f);
+  return FBR_OK;
+}
+
+int fbr_pg_add_between(fbr_ctx* c, int64_t i, int64_t j, const float between[16], const double variances[6]) {
+  if (!c || !between || !variances) return FBR_ERR_INVALID_ARG;
+  double Z[12];
+  for (int r = 0; r < 3; ++r) {
+    for (int q = 0; q < 3; ++q) Z[3 * r + q] = (double)between[4 * r + q];
+    Z[9 + r] = (double)between[4 * r + 3];
+  }
+  return add_between(c, i, j, Z, variances);
+}
+
+int fbr_pg_add_between_poses(fbr_ctx* c, int64_t i, int64_t j, const float pose_i[6], const float pose_j[6],
+                             const double variances[6]) {
+  if (!c || !pose_i || !pose_j || !variances) return FBR_ERR_INVALID_ARG;
+  double ei[6], ej[6], A[12], B[12], Z[12];
+  for (int k = 0; k < 6; ++k) {
+    ei[k] = (double)pose_i[k];
+    ej[k] = (double)pose_j[k];
+  }
+  pg_pose_from_euler(ei, A);
+  pg_pose_from_euler(ej, B);
+  pg_between(A, B, Z);
+  return add_between(c, i, j, Z, variances);
+}
+
+int fbr_pg_add_gps(fbr_ctx* c, int64_t node, const double xyz[3], const double variances[3]) {
+  if (!c || !xyz || !variances || !node_ok(c, node) || !variances_ok(variances, 3)) return FBR_ERR_INVALID_ARG;
+  PgFactor f{};
+  f.type = kPgGps;
+  f.i = (int32_t)node;
+  f.j = -1;
+  for (int k = 0; k < 3; ++k) {
+    if (!std::isfinite(xyz[k])) return FBR_ERR_INVALID_ARG;
+    f.Z[9 + k] = xyz[k];
+    f.w[3 + k] = 1.0 / std::sqrt(variances[k]);
+  }
+  c->pg_factors.push_back(f);
+  return FBR_OK;
+}
+
+int fbr_pg_add_loop(fbr_ctx* c, const fbr_loop_result* r, int* added) {
+  if (added) *added = 0;
+  if (!c || !r) return FBR_ERR_INVALID_ARG;
+  if (r->status != FBR_LOOP_CLOSED) return FBR_OK;
+  const double score = (double)(float)r->icp.fitness;  // noiseScore (:746)
+  const double var[6] = {score, score, score, score, score, score};
+  const int rc = fbr_pg_add_between(c, r->latest_id, r->closest_id, r->between, var);
+  if (!rc && added) *added = 1;
+  return rc;
+}
+
+int fbr_pg_factor_count(fbr_ctx* c, int64_t* n) {
+  if (!c || !n) return FBR_ERR_INVALID_ARG;
+  *n = (int64_t)c->pg_factors.size();
+  return FBR_OK;
+}
+
+int fbr_pg_optimize(fbr_ctx* c, const fbr_pg_params* p, fbr_pg_result* out) {
+  if (!c || !out || !pg_params_ok(p)) return FBR_ERR_INVALID_ARG;
+  CK(enter(c));
+  std::memset(out, 0, sizeof(*out));
+  return pg_run(c, *p, out);
+}
+
+int fbr_pg_poses(fbr_ctx* c, double* poses_out, int64_t cap, int64_t* n) {
+  if (!c || !n || cap < 0 || (cap && !poses_out)) return FBR_ERR_INVALID_ARG;
+  if (c->pg_result_n < 0) return FBR_ERR_STATE;
+  *n = c->pg_result_n;
+  if (cap < c->pg_result_n) return FBR_ERR_CAPACITY;
+  std::memcpy(poses_out, c->pg_result.data(), sizeof(double) * 6 * c->pg_result_n);
+  return FBR_OK;
+}
+
+int fbr_pg_apply(fbr_ctx* c) {
+  if (!c) return FBR_ERR_INVALID_ARG;
+  if (c->pg_result_n < 0 || c->pg_result_n != (int64_t)c->kf_poses.size()) return FBR_ERR_STATE;
+  for (int64_t i = 0; i < c->pg_result_n; ++i) {  // correctPoses (:1746-1757)
+    const double* e = &c->pg_result[6 * i];
+    fbr_keypose p = c->kf_poses[i];
+    p.roll = (float)e[0];
+    p.pitch = (float)e[1];
+    p.yaw = (float)e[2];
+    p.x = (float)e[3];
+    p.y = (float)e[4];
+    p.z = (float)e[5];
+    const int rc = fbr_keyframes_set_pose(c, i, &p);
+    if (rc) return rc;
+  }
+  return FBR_OK;
+}
+
+}  // extern "C"

@@ -136,6 +136,34 @@ def sc_params(**kw):
     return p
 
 
+# pose graph (include/fbr.h "pose graph")
+FBR_PG_CONVERGED, FBR_PG_ITERATIONS, FBR_PG_STALLED, FBR_PG_NUMERICAL, FBR_PG_EMPTY = range(5)
+
+
+class FbrPgParams(_Dictable):
+    _fields_ = [("max_iterations", ctypes.c_int32), ("max_pcg_iterations", ctypes.c_int32),
+                ("rel_cost_tol", ctypes.c_double), ("abs_cost_tol", ctypes.c_double), ("pcg_rel_tol", ctypes.c_double),
+                ("lambda_init", ctypes.c_double), ("lambda_factor", ctypes.c_double), ("lambda_max", ctypes.c_double),
+                ("reserved_", ctypes.c_int32 * 4)]
+
+
+class FbrPgResult(_Dictable):
+    _fields_ = [("status", ctypes.c_int32), ("iterations", ctypes.c_int32), ("trials", ctypes.c_int32),
+                ("pcg_iterations", ctypes.c_int32), ("n_nodes", ctypes.c_int32), ("n_factors", ctypes.c_int32),
+                ("n_loop_factors", ctypes.c_int32), ("pad_", ctypes.c_int32), ("cost_initial", ctypes.c_double),
+                ("cost_final", ctypes.c_double), ("lambda", ctypes.c_double),
+                ("max_translation_change", ctypes.c_double), ("max_rotation_change", ctypes.c_double)]
+
+
+def pg_params(**kw):
+    """fbr_pg_params_default: 30 LM steps, 200 PCG iterations, GTSAM's 1e-5 error tolerances, PCG 1e-8,
+    lambda 1e-5 x 10 up to 1e10."""
+    p = FbrPgParams(30, 200, 1e-5, 1e-5, 1e-8, 1e-5, 10.0, 1e10)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

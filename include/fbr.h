@@ -267,9 +267,9 @@ int fbr_set_deskew(fbr_ctx* ctx, const fbr_deskew_table* tables, int n_tables);
  * each scan against a local map built from its keyframes instead of the cropped prior map:
  * extractSurroundingKeyFrames (:964-978) -> extractNearby (:872-907) or extractForLoopClosure
  * (:857-870) -> extractCloud (:909-955).  The keyframe store mirrors cloudKeyPoses3D/6D and
- * corner/surfCloudKeyFrames; GTSAM (saveKeyFramesAndFactor / correctPoses) stays with the caller,
- * which pushes each new key pose + its down-sampled feature clouds (fbr_keyframes_add) and
- * rewrites poses after a loop closure (fbr_keyframes_set_pose).  Selection runs on the host (a few
+ * corner/surfCloudKeyFrames; the caller pushes each new key pose + its down-sampled feature clouds
+ * (fbr_keyframes_add) and rewrites poses after a loop closure, from its own GTSAM graph
+ * (fbr_keyframes_set_pose) or from the pose graph below (fbr_pg_apply).  Selection runs on the host (a few
  * hundred poses), the transforms, concatenation, VoxelGrids and the kNN grid on the device. */
 typedef struct fbr_keypose {   /* PointXYZIRPYT (mapOptmization.h:34-51) */
   float x, y, z;
@@ -306,9 +306,10 @@ int fbr_extract_surrounding_keyframes(fbr_ctx* ctx, double stamp, const fbr_keyf
 
 /* ---- loop closure (detectLoopClosure / performLoopClosure, mapOptmization.h:606-782) -----------
  * The candidate search runs on the host over the key poses; the clouds, their VoxelGrid and the
- * ICP stay in HBM (the keyframe clouds fbr_keyframes_add stored: no cloud crosses PCIe).  GTSAM
- * stays with the caller: fbr_perform_loop_closure returns the between-factor to add, the caller
- * runs its pose graph and rewrites the key poses with fbr_keyframes_set_pose.  The loop calls
+ * ICP stay in HBM (the keyframe clouds fbr_keyframes_add stored: no cloud crosses PCIe).
+ * fbr_perform_loop_closure returns the between-factor to add: to the pose graph below
+ * (fbr_pg_add_loop, fbr_pg_optimize, fbr_pg_apply), or to the caller's own GTSAM graph, which then
+ * rewrites the key poses with fbr_keyframes_set_pose.  The loop calls
  * change no key pose and touch neither the registration map, its grids nor a keyframe local map.
  *
  * detectLoopClosure (:606-674) at timeLaserCloudInfoLast = `stamp`:
@@ -514,6 +515,126 @@ int fbr_sc_detect_loop_closure(fbr_ctx* ctx, double stamp, const fbr_loop_params
  * touched. */
 int fbr_perform_loop_closure_sc(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, const fbr_sc_params* sp,
                                 fbr_loop_result* out, fbr_sc_match* match);
+
+/* ---- pose graph: key poses from odometry, loop and GPS factors ----------------------
+ * The reference's addOdomFactor (:1517-1541), addGPSFactor (:1543-1634), the loop BetweenFactor
+ * (:743-758) and correctPoses (:1735-1770), as a batch optimiser over the keyframe store, so that
+ * "loop closed" can end in corrected key poses without GTSAM.  This is the project's own
+ * restatement: it is pinned by a NumPy model in tests/ and not against GTSAM or iSAM2.  What stays
+ * with the caller: iSAM2's incremental updates, marginal covariances (poseCovariance, and with it
+ * addGPSFactor's covariance gate), robust kernels and IMU preintegration factors.
+ *
+ * Nodes 0 .. N-1 are the keyframes in the store when fbr_pg_optimize is called; node i starts from
+ * the stored key pose i.  A pose is (R, t), R = Rz(yaw) Ry(pitch) Rx(roll) as fbr_affine_from_pose;
+ * all optimiser arithmetic is double (csrc/fbr_pg.h, compiled for the device and for the CPU probe
+ * of the tests; no FMA contraction).
+ *
+ * Chart: GTSAM 4.0's default for Pose3 (no GTSAM_POSE3_EXPMAP):
+ *   retraction  T (+) [w; v]  = (R Exp(w), t + R v)
+ *   Local(A, B)               = [Log(A_R^T B_R); A_R^T (B_t - A_t)]
+ *   tangent order [rotation; translation], the reference's noise vectors (roll, pitch, yaw, x, y, z).
+ *
+ * Factors; each carries variances and its residual is whitened by 1 / sqrt(variance):
+ *   prior(i, Z, var[6])       e = Local(Z, T_i)             PriorFactor<Pose3>, :1523-1525
+ *   between(i, j, Z, var[6])  e = Local(Z, T_i^-1 T_j)      BetweenFactor<Pose3>, :1531-1537, :758
+ *   gps(i, z, var[3])         e = T_i.t - z                 gtsam::GPSFactor, :1627
+ * Cost F = 1/2 sum_k |e_k / sigma_k|^2.
+ *
+ * Jacobians, analytic, with respect to the chart.  With D = T_i^-1 T_j, E = Z^-1 D, phi = Log(E_R):
+ *   d e_rot / d w_j = Jr^-1(phi)              d e_t / d v_j = E_R
+ *   d e_rot / d w_i = -Jr^-1(phi) D_R^T       d e_t / d w_i = Z_R^T [D_t]x      d e_t / d v_i = -Z_R^T
+ *   Jr^-1(phi) = I + [phi]x / 2 + (1 / t^2 - (1 + cos t) / (2 t sin t)) [phi]x^2, t = |phi| (the
+ *   series 1/12 + t^2/720 below t = 1e-3; the second term evaluated as cot(t / 2) / (2 t))
+ *   prior: the j half with E = Z^-1 T_i;  gps: d e / d v = R_i, d e / d w = 0.
+ *   Log: t = atan2(|vee(R - R^T)| / 2, (trace - 1) / 2); the axis from vee(R - R^T) while
+ *   cos t > -0.99, from the symmetric part of R near pi; the series below t = 1e-6.  No NaN at 0 or pi.
+ *
+ * Method: Levenberg-Marquardt on H = J^T J, g = J^T r.
+ *   step:   (H + lambda diag(H)) delta = -g
+ *   accept when the cost falls: lambda /= lambda_factor; otherwise lambda *= lambda_factor, retry
+ *   FBR_PG_CONVERGED   an accepted step's relative cost decrease < rel_cost_tol or its absolute
+ *                      decrease < abs_cost_tol; also a graph whose initial cost is exactly 0 (0 iterations)
+ *   FBR_PG_ITERATIONS  max_iterations accepted steps
+ *   FBR_PG_STALLED     lambda > lambda_max; the best poses so far are kept
+ *   FBR_PG_NUMERICAL   a Cholesky pivot of the solve was non-positive or non-finite (or the initial
+ *                      cost is not finite); the optimised poses equal the initial ones
+ *   FBR_PG_EMPTY       no keyframes
+ * The linear solve splits H = T + L: T, block-tridiagonal in 6x6 blocks, holds every prior, every
+ * gps factor, every between factor with |i - j| = 1 and the damping; L every other between factor
+ * (the loops).  Conjugate gradients preconditioned by an exact solve with T (block cyclic
+ * reduction): one iteration without loops, and with K loops T^-1 H is the identity plus a term of
+ * rank <= 6 K.  It stops when r^T M^-1 r <= pcg_rel_tol^2 r0^T M^-1 r0 or after max_pcg_iterations;
+ * the iterate is then used as it is (the accept test covers an inexact step).
+ * The result is defined by the minimiser, not by the path to it.
+ *
+ * Output: double [N][6] = [roll, pitch, yaw, x, y, z] with roll = atan2(R21, R22), pitch =
+ * asin(-R20) clamped, yaw = atan2(R10, R00); fbr_pg_apply rounds them to float.
+ *
+ * Two calls on the same store and factors return the same bytes: no float or double atomics, every
+ * sum is taken in a fixed order. */
+typedef struct fbr_pg_params {
+  int32_t max_iterations;      /* 30 accepted LM steps */
+  int32_t max_pcg_iterations;  /* 200 */
+  double rel_cost_tol;         /* 1e-5, GTSAM's relativeErrorTol */
+  double abs_cost_tol;         /* 1e-5, GTSAM's absoluteErrorTol */
+  double pcg_rel_tol;          /* 1e-8 */
+  double lambda_init;          /* 1e-5 */
+  double lambda_factor;        /* 10 */
+  double lambda_max;           /* 1e10 */
+  int32_t reserved_[4];
+} fbr_pg_params;
+
+/* fbr_pg_result.status */
+#define FBR_PG_CONVERGED 0
+#define FBR_PG_ITERATIONS 1
+#define FBR_PG_STALLED 2
+#define FBR_PG_NUMERICAL 3
+#define FBR_PG_EMPTY 4
+
+typedef struct fbr_pg_result {
+  int32_t status;              /* FBR_PG_* */
+  int32_t iterations;          /* accepted LM steps */
+  int32_t trials;              /* accepted and rejected */
+  int32_t pcg_iterations;      /* total */
+  int32_t n_nodes;
+  int32_t n_factors;
+  int32_t n_loop_factors;      /* factors in L */
+  int32_t pad_;
+  double cost_initial;
+  double cost_final;
+  double lambda;
+  double max_translation_change;  /* over the nodes, optimised against stored */
+  double max_rotation_change;
+} fbr_pg_result;
+
+void fbr_pg_params_default(fbr_pg_params* p);
+/* Empties the factor list (fbr_keyframes_reset does the same). */
+int fbr_pg_reset(fbr_ctx* ctx);
+/* Factors.  Node indices must name existing keyframes, variances must be finite and > 0, measurements
+ * finite, i != j: otherwise FBR_ERR_INVALID_ARG and nothing is stored.  `between` is row-major, as
+ * fbr_loop_result.between, and is taken as it is (its rotation block is not re-orthonormalised). */
+int fbr_pg_add_prior(fbr_ctx* ctx, int64_t node, const float pose[6], const double variances[6]);
+int fbr_pg_add_between(fbr_ctx* ctx, int64_t i, int64_t j, const float between[16], const double variances[6]);
+/* poseFrom.between(poseTo) computed in double: odometry is added this way (:1533-1537). */
+int fbr_pg_add_between_poses(fbr_ctx* ctx, int64_t i, int64_t j, const float pose_i[6], const float pose_j[6],
+                             const double variances[6]);
+int fbr_pg_add_gps(fbr_ctx* ctx, int64_t node, const double xyz[3], const double variances[3]);
+/* With r->status == FBR_LOOP_CLOSED: the between factor (latest_id, closest_id, r->between,
+ * (float)r->icp.fitness x 6) of :746-758, *added (optional) = 1; otherwise nothing, *added = 0. */
+int fbr_pg_add_loop(fbr_ctx* ctx, const fbr_loop_result* r, int* added);
+int fbr_pg_factor_count(fbr_ctx* ctx, int64_t* n);
+/* Optimises the key poses under the factors.  Changes no key pose, no map and no grid.  A node that
+ * no factor touches: FBR_ERR_STATE.  A graph without a prior is allowed (the damping makes it
+ * solvable).  One host read per Levenberg-Marquardt trial; the conjugate-gradient iterations are
+ * enqueued ahead of a host-mapped progress word, as the ICP's. */
+int fbr_pg_optimize(fbr_ctx* ctx, const fbr_pg_params* p, fbr_pg_result* out);
+/* The last optimise's poses; *n = their count.  FBR_ERR_STATE without a result, FBR_ERR_CAPACITY
+ * (with *n set) if cap < *n. */
+int fbr_pg_poses(fbr_ctx* ctx, double* poses_out /* [n][6] */, int64_t cap, int64_t* n);
+/* correctPoses (:1735-1770): every key pose gets its optimised x, y, z, roll, pitch, yaw rounded to
+ * float through fbr_keyframes_set_pose (index and time kept).  FBR_ERR_STATE when there is no result
+ * or the store has changed size since the optimise. */
+int fbr_pg_apply(fbr_ctx* ctx);
 
 /* Down-sampled global map actually used (sizes, then optional copies; pass NULL to skip).  After
  * fbr_extract_surrounding_keyframes: the keyframe local map (laserCloud{Corner,Surf}FromMapDS). */

@@ -362,6 +362,45 @@ class MapOptimization {
     return r;
   }
 
+  /* Pose graph (include/fbr.h, "pose graph"): the factors of saveKeyFramesAndFactor (addOdomFactor
+   * :1517-1541, addGPSFactor :1543-1634, the loop BetweenFactor :743-758), a batch optimise in place
+   * of isam->update, and correctPoses (:1735-1770) for a host without GTSAM. */
+  void pgReset() { check(fbr_pg_reset(c_.get()), "fbr_pg_reset"); }
+  void pgAddPrior(int64_t node, const float pose[6], const double variances[6]) {
+    check(fbr_pg_add_prior(c_.get(), node, pose, variances), "fbr_pg_add_prior");
+  }
+  void pgAddBetween(int64_t i, int64_t j, const float between[16], const double variances[6]) {
+    check(fbr_pg_add_between(c_.get(), i, j, between, variances), "fbr_pg_add_between");
+  }
+  void pgAddBetweenPoses(int64_t i, int64_t j, const float pose_i[6], const float pose_j[6], const double variances[6]) {
+    check(fbr_pg_add_between_poses(c_.get(), i, j, pose_i, pose_j, variances), "fbr_pg_add_between_poses");
+  }
+  void pgAddGps(int64_t node, const double xyz[3], const double variances[3]) {
+    check(fbr_pg_add_gps(c_.get(), node, xyz, variances), "fbr_pg_add_gps");
+  }
+  bool pgAddLoop(const fbr_loop_result& r) {
+    int added = 0;
+    check(fbr_pg_add_loop(c_.get(), &r, &added), "fbr_pg_add_loop");
+    return added != 0;
+  }
+  int64_t pgFactorCount() {
+    int64_t n = 0;
+    check(fbr_pg_factor_count(c_.get(), &n), "fbr_pg_factor_count");
+    return n;
+  }
+  /* poses (optional) receives [n_nodes][6] doubles = [roll, pitch, yaw, x, y, z]; no key pose changes */
+  fbr_pg_result pgOptimize(const fbr_pg_params& pp, std::vector<double>* poses = nullptr) {
+    fbr_pg_result r{};
+    check(fbr_pg_optimize(c_.get(), &pp, &r), "fbr_pg_optimize");
+    if (poses) {
+      poses->assign((size_t)r.n_nodes * 6, 0.0);
+      int64_t n = 0;
+      if (r.n_nodes > 0) check(fbr_pg_poses(c_.get(), poses->data(), r.n_nodes, &n), "fbr_pg_poses");
+    }
+    return r;
+  }
+  void correctPoses() { check(fbr_pg_apply(c_.get()), "fbr_pg_apply"); }
+
  private:
   Context& c_;
   double timeLastProcessing_ = -1.0;  // mapOptmization.h:135 (timeLastProcessing = -1)
