@@ -16,8 +16,8 @@ import os
 import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
-                        FbrLoopResult, FbrParams, FbrPgResult, FbrRegStats, FbrScMatch, PointCloud2, default_params,
-                        icp_params, loop_params, pg_params, ptr, sc_params)
+                        FbrGmapResult, FbrLoopResult, FbrParams, FbrPgResult, FbrRegStats, FbrScMatch, PointCloud2,
+                        default_params, gmap_params, icp_params, loop_params, pg_params, ptr, sc_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = [
     "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
     "fbr_pg_params_default", "fbr_pg_reset", "fbr_pg_add_prior", "fbr_pg_add_between", "fbr_pg_add_between_poses",
     "fbr_pg_add_gps", "fbr_pg_add_loop", "fbr_pg_factor_count", "fbr_pg_optimize", "fbr_pg_poses", "fbr_pg_apply",
+    "fbr_gmap_params_default", "fbr_global_map_build", "fbr_global_map_get", "fbr_global_map_install",
+    "fbr_global_map_save", "fbr_pcd_write_poses_ascii", "fbr_selftest_voxel_wide",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -149,6 +151,13 @@ def lib():
             "fbr_pg_optimize": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_pg_poses": (ctypes.c_int, [_VP, _VP, _I64, _VP]),
             "fbr_pg_apply": (ctypes.c_int, [_VP]),
+            "fbr_gmap_params_default": (None, [_VP]),
+            "fbr_global_map_build": (ctypes.c_int, [_VP, _VP, _VP]),
+            "fbr_global_map_get": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
+            "fbr_global_map_install": (ctypes.c_int, [_VP]),
+            "fbr_global_map_save": (ctypes.c_int, [_VP, ctypes.c_char_p, _I32]),
+            "fbr_pcd_write_poses_ascii": (ctypes.c_int, [ctypes.c_char_p, _VP, _I64]),
+            "fbr_selftest_voxel_wide": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_float, _VP, _VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
             "fbr_comm_create_local": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int]),
@@ -335,6 +344,14 @@ def pcd_write(path, points, binary=False):
     pts = _as_points(points, POINT_XYZI)
     f = lib().fbr_pcd_write_binary if binary else lib().fbr_pcd_write_ascii
     _check(f(os.fsencode(path), ptr(pts) if len(pts) else None, len(pts)), f"fbr_pcd_write({path})")
+
+
+def pcd_write_poses(path, keyposes):
+    """savePCDFileASCII of cloudKeyPoses6D (transformations.pcd, mapOptmization.h:499): KEYPOSE records
+    as x y z intensity roll pitch yaw time (host only)."""
+    kp = _as_points(np.atleast_1d(keyposes), KEYPOSE)
+    _check(lib().fbr_pcd_write_poses_ascii(os.fsencode(path), ptr(kp) if len(kp) else None, len(kp)),
+           f"fbr_pcd_write_poses_ascii({path})")
 
 
 def msg_to_points(msg):
@@ -716,6 +733,43 @@ class Context:
         """correctPoses: the optimised poses, rounded to float, become the key poses."""
         _check(lib().fbr_pg_apply(self._h), "fbr_pg_apply")
 
+    # ---- global map (mapOptmization.h:485-521) ----
+    def global_map_build(self, params=None, raw=False, **kw):
+        """Build the global map from every keyframe at its current key pose (params: gmap_params(), or
+        its fields as keywords).  Returns fbr_gmap_result as a dict (raw: the FbrGmapResult itself)."""
+        p = params if params is not None else gmap_params(**kw)
+        r = FbrGmapResult()
+        _check(lib().fbr_global_map_build(self._h, ctypes.byref(p), ctypes.byref(r)), "fbr_global_map_build")
+        return r if raw else r.as_dict()
+
+    def global_map(self):
+        """The built (corner, surf) clouds."""
+        nc, ns = _I64(), _I64()
+        _check(lib().fbr_global_map_get(self._h, ctypes.byref(nc), ctypes.byref(ns), None, None), "fbr_global_map_get")
+        c = np.zeros(max(nc.value, 1), POINT_XYZI)
+        s = np.zeros(max(ns.value, 1), POINT_XYZI)
+        _check(lib().fbr_global_map_get(self._h, None, None, ptr(c), ptr(s)), "fbr_global_map_get")
+        return c[:nc.value].copy(), s[:ns.value].copy()
+
+    def global_map_install(self):
+        """What set_map(*global_map()) does, without the clouds leaving the device."""
+        _check(lib().fbr_global_map_install(self._h), "fbr_global_map_install")
+
+    def global_map_save(self, directory, cloud_global=False):
+        """cloudCorner.pcd, cloudSurf.pcd, trajectory.pcd, transformations.pcd (and cloudGlobal.pcd when
+        asked for and the build kept the raw clouds) into the existing `directory`."""
+        _check(lib().fbr_global_map_save(self._h, os.fsencode(directory), 1 if cloud_global else 0),
+               "fbr_global_map_save")
+
+    def selftest_voxel_wide(self, pts, leaf):
+        """The wide (64-bit key) VoxelGrid alone on a host cloud, overflowing or not."""
+        pts = _as_points(pts, POINT_XYZI)
+        out = np.zeros(max(len(pts), 1), POINT_XYZI)
+        n = _I64()
+        _check(lib().fbr_selftest_voxel_wide(self._h, ptr(pts) if len(pts) else None, len(pts), ctypes.c_float(leaf),
+                                             ptr(out), ctypes.byref(n)), "fbr_selftest_voxel_wide")
+        return out[:n.value].copy()
+
     def relocalize(self, points, k=4, sc=None):
         """Find the pose of one raw scan (POINT_XYZIRT) without a guess: project, extract features,
         down-sample them at the two mapping leaves, sc_query, then register from each hypothesis in
@@ -908,6 +962,6 @@ class Comm:
 
 
 __all__ = ["Context", "Comm", "comm_unique_id", "FbrError", "FbrParams", "default_params", "lib", "device_count",
-           "affine_from_pose", "pose_from_affine", "pcd_read", "pcd_write", "msg_to_points", "points_to_msg", "PointCloud2",
+           "affine_from_pose", "pose_from_affine", "pcd_read", "pcd_write", "pcd_write_poses", "msg_to_points", "points_to_msg", "PointCloud2",
            "imu_convert", "imu_deskew_info",
            "EXPORTED_SYMBOLS"]

@@ -10,6 +10,7 @@
 //   fbr_loop.hip    loop closure candidate search and ICP
 //   fbr_sc.hip      scan-context place recognition: descriptor store, search, loop closure under drift
 //   fbr_pg.hip      pose graph: the factor list, the Levenberg-Marquardt driver, correctPoses
+//   fbr_gmap.hip    global map: build from the keyframe store, get, install, save
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -473,6 +474,20 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   unsigned long long* d_pg_flag = nullptr;  // not owning: h_pg_flag's device address
   unsigned long long pg_gen = 0;
 
+  // ---- global map (fbr_gmap.hip) ----
+  // The clouds of the last fbr_global_map_build, until the next build, fbr_keyframes_reset or
+  // fbr_destroy; the raw concatenations only when that build kept them.
+  bool gm_built = false, gm_has_raw = false;
+  Dev<float4> d_gm_c, d_gm_s, d_gm_raw_c, d_gm_raw_s;
+  int64_t gm_c_n = 0, gm_s_n = 0, gm_raw_c_n = 0, gm_raw_s_n = 0;
+  std::vector<fbr_keypose> gm_poses;  // the key poses that build used
+  GrowDev<KfSeg> d_gm_segs;           // a build's entries, corner then surf
+  // the map fbr_global_map_install put in place, in map-index order: fbr_get_map's source while
+  // map_host_stale says that map_*_host have not been filled from it yet (fbr_map.hip)
+  Dev<float4> d_inst_c, d_inst_s;
+  int64_t inst_c_n = 0, inst_s_n = 0;
+  bool map_host_stale = false;
+
   // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;
   std::set<std::string> profile_only;  // empty: time every kernel
@@ -536,6 +551,10 @@ int check_err(fbr_ctx* c, int B);
 int drop_staged_batch(fbr_ctx* c);
 // fbr_map.hip
 int voxel_grid_dev(fbr_ctx* c, const float4* d_in, int64_t n, float leaf, float4* d_out, int64_t* n_out);
+// fbr_set_map on clouds that are on the device already (fbr_global_map_install)
+int set_map_device(fbr_ctx* c, const float4* d_corner, int64_t n_corner, const float4* d_surf, int64_t n_surf);
+// fbr_gmap.hip
+void gmap_drop(fbr_ctx* c);  // forgets the built global map (fbr_keyframes_reset)
 // fbr_loop.hip
 bool loop_params_ok(const fbr_loop_params* lp);
 // performLoopClosure for a given candidate pair; latest_pose (null: the stored one) stands for the

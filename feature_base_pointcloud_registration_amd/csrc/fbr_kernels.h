@@ -6,8 +6,10 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 
 #include "fbr_common.h"
+#include "fbr_gmap.h"
 #include "fbr_pg.h"
 
 namespace fbr {
@@ -234,6 +236,36 @@ inline void arena_free(DevArena& a) {
 // (Callers take it from knobs::vg_large_min() points on: below, the one-workgroup kernel is faster.)
 int voxel_grid_large(hipStream_t s, DevArena& ar, const float4* in, int64_t n, float leaf, int morton, int exact,
                      float4* out, int32_t* d_nout);
+
+// The wide VoxelGrid (k_gmap.hip): PCL's grid with 64-bit keys (fbr_gmap.h), for clouds PCL's own
+// filter refuses.  The input is a concatenation described by KfSeg entries over a point pool and
+// never written out.
+struct KfSeg;
+struct GmapSrc {
+  const float4* pool;  // device
+  const KfSeg* segs;   // device: ascending dst, no empty entry, [src, src + count) inside the pool
+  int nseg;
+  int xform;           // 0: the entries' T is ignored (a plain cloud)
+  int64_t n;           // points of the concatenation (the entries' counts added up)
+  int64_t max_count;   // the largest entry
+};
+struct GmapInfo {
+  GmapGrid G;
+  int32_t has_grid;    // 0: no finite point, G is not set
+  int32_t pad_;
+  int64_t n_dropped, n_out;  // points with a non-finite coordinate; voxels written (voxel_grid_wide)
+};
+// getMinMax3D of the concatenation's finite points, the count of the others, and the grid at `leaf`.
+// Synchronises the stream.
+int gmap_bounds(hipStream_t s, DevArena& ar, const GmapSrc& src, float leaf, GmapInfo* info);
+// The points of in[0 .. n) whose x, y, z are finite, in order, into out[0 .. n_out) (n_out = n less
+// gmap_bounds' n_dropped).  Enqueued on s; the arena holds its scratch until the stream has run it.
+int gmap_compact_finite(hipStream_t s, DevArena& ar, const float4* in, int64_t n, float4* out, int64_t n_out);
+// Voxels in ascending key order into alloc_out(n_out) (called once the count is known; null fails
+// the call), centroids summed in index order.  bounds: gmap_bounds' result for the same src and
+// leaf, or null.  FBR_ERR_CAPACITY beyond fbr_gmap.h's limits or INT32_MAX points.  Synchronises.
+int voxel_grid_wide(hipStream_t s, DevArena& ar, const GmapSrc& src, float leaf, const GmapInfo* bounds,
+                    const std::function<float4*(int64_t)>& alloc_out, GmapInfo* info);
 
 // Per-ring surf filter reading the projected cloud + label mask directly (no candidate copy).
 struct VgRing {

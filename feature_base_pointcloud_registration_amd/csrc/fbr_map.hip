@@ -1,4 +1,5 @@
-// fbr_map.hip — the registration map: the start-up VoxelGrid and the kNN grids of fbr_set_map, the
+// fbr_map.hip — the registration map: the start-up VoxelGrid and the kNN grids of fbr_set_map (and of
+// set_map_device, the same steps on clouds already in HBM, for fbr_global_map_install), the
 // keyframe store and the local map fbr_extract_surrounding_keyframes builds from it, and the
 // pose / affine helpers.
 #include "fbr_ctx.h"
@@ -140,6 +141,32 @@ float key_distance(const fbr_keypose& a, const fbr_keypose& b) {
 
 }  // namespace
 
+namespace fbr {
+namespace internal {
+
+// fbr_set_map's steps on device-resident clouds: the start-up VoxelGrids, then the grids.  The DS
+// maps stay in d_inst_c / d_inst_s; fbr_get_map fills the host copies from them on demand.
+int set_map_device(fbr_ctx* c, const float4* d_corner, int64_t n_corner, const float4* d_surf, int64_t n_surf) {
+  c->crop_cached = false;
+  c->map_nocrop = false;
+  c->map_c_host.clear();
+  c->map_s_host.clear();
+  c->map_host_stale = false;
+  c->has_map = false;
+  c->inst_c_n = c->inst_s_n = 0;
+  if (dalloc(c->d_inst_c, std::max<int64_t>(n_corner, 1)) || dalloc(c->d_inst_s, std::max<int64_t>(n_surf, 1)))
+    return FBR_ERR_HIP;
+  int rc = voxel_grid_dev(c, d_corner, n_corner, c->P.mapping_corner_leaf_size, c->d_inst_c, &c->inst_c_n);
+  if (!rc) rc = voxel_grid_dev(c, d_surf, n_surf, c->P.mapping_surf_leaf_size, c->d_inst_s, &c->inst_s_n);
+  if (!rc) rc = build_map_grids(c, c->d_inst_c, c->inst_c_n, c->d_inst_s, c->inst_s_n);
+  c->has_map = rc == FBR_OK;
+  c->map_host_stale = rc == FBR_OK;
+  return rc;
+}
+
+}  // namespace internal
+}  // namespace fbr
+
 extern "C" {
 
 int fbr_set_map(fbr_ctx* c, const fbr_point_xyzi* corner, int64_t n_corner, const fbr_point_xyzi* surf,
@@ -148,6 +175,9 @@ int fbr_set_map(fbr_ctx* c, const fbr_point_xyzi* corner, int64_t n_corner, cons
   CK(enter(c));
   c->crop_cached = false;
   c->map_nocrop = false;
+  c->map_host_stale = false;  // an installed map (fbr_global_map_install) is replaced
+  c->d_inst_c.reset();
+  c->d_inst_s.reset();
   int rc = voxel_grid_once(c, corner, n_corner, c->P.mapping_corner_leaf_size, c->map_c_host);
   if (!rc) rc = voxel_grid_once(c, surf, n_surf, c->P.mapping_surf_leaf_size, c->map_s_host);
   // the DS maps (map-index order) go to HBM once; the grids are built there
@@ -188,6 +218,16 @@ int fbr_get_map(fbr_ctx* c, int64_t* n_corner, int64_t* n_surf, fbr_point_xyzi* 
     if (corner && c->kds_c_n) CK(fbr_memcpy_sync(corner, c->d_kds_c, sizeof(float4) * c->kds_c_n, hipMemcpyDeviceToHost));
     if (surf && c->kds_s_n) CK(fbr_memcpy_sync(surf, c->d_kds_s, sizeof(float4) * c->kds_s_n, hipMemcpyDeviceToHost));
     return FBR_OK;
+  }
+  if (c->map_host_stale) {  // installed from the device (fbr_global_map_install): fetched on first use
+    CK(enter(c));
+    c->map_c_host.resize((size_t)c->inst_c_n);
+    c->map_s_host.resize((size_t)c->inst_s_n);
+    if (c->inst_c_n)
+      CK(fbr_memcpy_sync(c->map_c_host.data(), c->d_inst_c, sizeof(float4) * c->inst_c_n, hipMemcpyDeviceToHost));
+    if (c->inst_s_n)
+      CK(fbr_memcpy_sync(c->map_s_host.data(), c->d_inst_s, sizeof(float4) * c->inst_s_n, hipMemcpyDeviceToHost));
+    c->map_host_stale = false;
   }
   if (n_corner) *n_corner = (int64_t)c->map_c_host.size();
   if (n_surf) *n_surf = (int64_t)c->map_s_host.size();
@@ -291,6 +331,7 @@ int fbr_keyframes_reset(fbr_ctx* c) {
   c->sc_n = 0;  // the scan-context descriptors go with their keyframes (fbr_sc.hip)
   c->pg_factors.clear();  // ... and so do the pose graph's factors and its result (fbr_pg.hip)
   c->pg_result_n = -1;
+  gmap_drop(c);  // ... and the global map built from them (fbr_gmap.hip)
   return FBR_OK;
 }
 
@@ -404,6 +445,9 @@ int fbr_extract_surrounding_keyframes(fbr_ctx* c, double stamp, const fbr_keyfra
   c->crop_cached = false;
   c->map_c_host.clear();
   c->map_s_host.clear();
+  c->map_host_stale = false;
+  c->d_inst_c.reset();
+  c->d_inst_s.reset();
   if (rc) return rc;
   if (n_corner_map) *n_corner_map = c->kds_c_n;
   if (n_surf_map) *n_surf_map = c->kds_s_n;

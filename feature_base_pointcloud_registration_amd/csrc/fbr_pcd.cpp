@@ -304,6 +304,31 @@ int fbr_pcd_write_ascii(const char* path, const fbr_point_xyzi* pts, int64_t n) 
   return ok ? FBR_OK : FBR_ERR_INVALID_ARG;
 }
 
+// savePCDFileASCII of cloudKeyPoses6D (mapOptmization.h:499): a PointXYZIRPYT cloud.  The field list
+// is this project's reading of the point type's registration (:44-51: x y z intensity roll pitch yaw
+// as float, time as double); it has not been compared with a file PCL wrote.
+int fbr_pcd_write_poses_ascii(const char* path, const fbr_keypose* poses, int64_t n) {
+  if (!path || n < 0 || (n && !poses)) return FBR_ERR_INVALID_ARG;
+  FILE* f = std::fopen(path, "wb");
+  if (!f) return FBR_ERR_INVALID_ARG;
+  bool ok = std::fprintf(f,
+                         "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\n"
+                         "FIELDS x y z intensity roll pitch yaw time\nSIZE 4 4 4 4 4 4 4 8\nTYPE F F F F F F F F\n"
+                         "COUNT 1 1 1 1 1 1 1 1\nWIDTH %lld\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %lld\nDATA ascii\n",
+                         (long long)n, (long long)n) > 0;
+  for (int64_t i = 0; i < n && ok; ++i) {
+    const fbr_keypose& p = poses[i];
+    const double v[8] = {p.x, p.y, p.z, p.intensity, p.roll, p.pitch, p.yaw, p.time};
+    for (int c = 0; c < 8 && ok; ++c) {
+      if (std::isnan(v[c])) ok = std::fputs("nan", f) >= 0;
+      else ok = std::fprintf(f, "%.8g", v[c]) > 0;
+      if (ok) ok = std::fputc(c < 7 ? ' ' : '\n', f) != EOF;
+    }
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? FBR_OK : FBR_ERR_INVALID_ARG;
+}
+
 int fbr_pcd_write_binary(const char* path, const fbr_point_xyzi* pts, int64_t n) {
   if (!path || n < 0 || (n && !pts)) return FBR_ERR_INVALID_ARG;
   FILE* f = std::fopen(path, "wb");

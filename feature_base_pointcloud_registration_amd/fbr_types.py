@@ -164,6 +164,30 @@ def pg_params(**kw):
     return p
 
 
+# global map (include/fbr.h "global map")
+FBR_GMAP_SAVE_GLOBAL = 1
+
+
+class FbrGmapParams(_Dictable):
+    _fields_ = [("corner_leaf", ctypes.c_float), ("surf_leaf", ctypes.c_float), ("wide", ctypes.c_int32),
+                ("keep_raw", ctypes.c_int32), ("reserved_", ctypes.c_int32 * 4)]
+
+
+class FbrGmapResult(_Dictable):
+    _fields_ = [("n_keyframes", ctypes.c_int64), ("n_corner_raw", ctypes.c_int64), ("n_surf_raw", ctypes.c_int64),
+                ("n_corner", ctypes.c_int64), ("n_surf", ctypes.c_int64), ("n_dropped", ctypes.c_int64),
+                ("corner_overflow", ctypes.c_int32), ("surf_overflow", ctypes.c_int32),
+                ("corner_wide", ctypes.c_int32), ("surf_wide", ctypes.c_int32)]
+
+
+def gmap_params(**kw):
+    """fbr_gmap_params_default: the context's mapping leaves (0), PCL semantics (wide = 0), no raw clouds."""
+    p = FbrGmapParams(0.0, 0.0, 0, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

@@ -636,6 +636,87 @@ int fbr_pg_poses(fbr_ctx* ctx, double* poses_out /* [n][6] */, int64_t cap, int6
  * or the store has changed size since the optimise. */
 int fbr_pg_apply(fbr_ctx* ctx);
 
+/* ---- global map (visualizeGlobalMapThread's save block, mapOptmization.h:485-521) -------------
+ * Turns the keyframe store into the map the localiser loads: every keyframe's corner / surf cloud
+ * transformed by its current key pose (fbr_affine_from_pose on the host, then
+ * ((T0 x + T1 y) + T2 z) + T3 per row, as fbr_extract_surrounding_keyframes), concatenated in
+ * keyframe order, and filtered by downSizeFilterCorner / downSizeFilterSurf.  Everything happens in
+ * HBM on the clouds fbr_keyframes_add stored; the result stays in device buffers of the context
+ * until the next build, fbr_keyframes_reset or fbr_destroy.  A build changes neither the
+ * registration map, nor its grids, nor any key pose.
+ *
+ * Points with a non-finite coordinate after the transform are dropped (the reference leaves the
+ * case undefined) and counted in n_dropped; they belong to neither the filtered nor the raw clouds.
+ *
+ * Reference mode (wide = 0, the default): pcl::VoxelGrid's semantics, the filter every other
+ * entry point uses (exact_voxel_order applies).  PCL gives up when its cell count
+ * dx * dy * dz exceeds INT32_MAX ("Leaf size is too small") and returns its input: the cloud is
+ * then the unfiltered concatenation and *_overflow is set.  At the 0.2 m corner leaf that limit is
+ * roughly a 250 m cube, which any real trajectory exceeds.
+ *
+ * Wide mode (wide = 1) is this project's own extension, not the reference's behaviour: where PCL
+ * would overflow, the cloud is filtered by a VoxelGrid with 64-bit keys; where it would not, by the
+ * normal filter (the two modes then return the same bytes).  The wide filter:
+ *   - inv, min_b, max_b, div_b and ijk exactly as PCL's: the float min / max box and
+ *     ijk = (int)(floorf(p * inv) - (float)min_b);
+ *   - key = ijk0 + ijk1 * div0 + ijk2 * div0 * div1 in uint64; voxels in ascending key order;
+ *   - centroid = the float sum of x, y, z, intensity over the voxel's points in input index order,
+ *     divided by the float count; exact_voxel_order has no meaning here (PCL has no order to
+ *     reproduce on overflow) and is ignored;
+ *   - FBR_ERR_CAPACITY when div0 * div1 * div2 >= 2^63, when some |bound * inv| >= 2^24
+ *     (floorf(p * inv) stops being an exact cell number) or for more than INT32_MAX points;
+ *   - no float atomics: two calls return the same bytes. */
+typedef struct fbr_gmap_params {
+  float corner_leaf, surf_leaf;   /* <= 0: fbr_params.mapping_corner_leaf_size / mapping_surf_leaf_size */
+  int32_t wide;                   /* 0 (default): PCL semantics, overflow -> output = input;
+                                     1: the wide filter where PCL would overflow, the normal path otherwise */
+  int32_t keep_raw;               /* keep the unfiltered concatenations (cloudGlobal.pcd) */
+  int32_t reserved_[4];
+} fbr_gmap_params;
+
+typedef struct fbr_gmap_result {
+  int64_t n_keyframes, n_corner_raw, n_surf_raw, n_corner, n_surf, n_dropped;
+  int32_t corner_overflow, surf_overflow;   /* PCL's overflow condition held */
+  int32_t corner_wide, surf_wide;           /* the wide filter produced the cloud */
+} fbr_gmap_result;
+
+#define FBR_GMAP_SAVE_GLOBAL 1  /* fbr_global_map_save: also cloudGlobal.pcd */
+
+/* corner_leaf = surf_leaf = 0 (the context's mapping leaves), wide = 0, keep_raw = 0. */
+void fbr_gmap_params_default(fbr_gmap_params* p);
+/* Builds the map from all keyframes in index order (params NULL: the defaults; result optional).
+ * n_*_raw count the concatenations' points after the drop.  With no keyframes: FBR_OK, all counts 0
+ * (an empty map is built). */
+int fbr_global_map_build(fbr_ctx* ctx, const fbr_gmap_params* params, fbr_gmap_result* result);
+/* The built clouds (sizes, then optional copies; pass NULL to skip), as fbr_get_map.
+ * FBR_ERR_STATE when no build has been done. */
+int fbr_global_map_get(fbr_ctx* ctx, int64_t* n_corner, int64_t* n_surf, fbr_point_xyzi* corner,
+                       fbr_point_xyzi* surf);
+/* Exactly what fbr_set_map does on the built clouds: the start-up VoxelGrid at the
+ * context's mapping leaves, the kNN grids, registration with the CropBox.  The built clouds are
+ * filtered and gridded where they are (no cloud is uploaded); fbr_get_map downloads the installed
+ * map when it is asked for.  FBR_ERR_STATE when no build has been done. */
+int fbr_global_map_install(fbr_ctx* ctx);
+/* Writes the reference's files into the existing directory `dir` (:495-519), never removing
+ * anything (the reference's `rm -r` of the directory is not reproduced):
+ *   cloudCorner.pcd, cloudSurf.pcd   the built clouds (fbr_pcd_write_ascii)
+ *   trajectory.pcd                   x, y, z, intensity of the key poses the build used (cloudKeyPoses3D)
+ *   transformations.pcd              those key poses (cloudKeyPoses6D, fbr_pcd_write_poses_ascii)
+ *   cloudGlobal.pcd                  raw corner then raw surf; only with FBR_GMAP_SAVE_GLOBAL in
+ *                                    flags and a build that kept them (keep_raw)
+ * FBR_ERR_STATE when no build has been done, FBR_ERR_INVALID_ARG when a file cannot be written. */
+int fbr_global_map_save(fbr_ctx* ctx, const char* dir, int32_t flags);
+/* pcl::io::savePCDFileASCII of a PointXYZIRPYT cloud (host only): FIELDS x y z intensity roll pitch
+ * yaw time, SIZE 4 4 4 4 4 4 4 8, TYPE F F F F F F F F, COUNT 1 each; values by fbr_pcd_write_ascii's
+ * rules (8 significant digits, "nan" spelled out), `time` too.  The layout is this project's reading
+ * of PCL's field registration for PointXYZIRPYT (mapOptmization.h:34-51); it has not been pinned
+ * against PCL's own writer. */
+int fbr_pcd_write_poses_ascii(const char* path, const fbr_keypose* keyposes, int64_t n);
+/* Test hook: the wide filter alone on a host cloud, whether PCL would overflow on it or not
+ * (points with a non-finite coordinate are skipped, as fbr_voxel_grid does).  out holds n points. */
+int fbr_selftest_voxel_wide(fbr_ctx* ctx, const fbr_point_xyzi* in, int64_t n, float leaf, fbr_point_xyzi* out,
+                            int64_t* n_out);
+
 /* Down-sampled global map actually used (sizes, then optional copies; pass NULL to skip).  After
  * fbr_extract_surrounding_keyframes: the keyframe local map (laserCloud{Corner,Surf}FromMapDS). */
 int fbr_get_map(fbr_ctx* ctx, int64_t* n_corner, int64_t* n_surf, fbr_point_xyzi* corner,

@@ -401,6 +401,29 @@ class MapOptimization {
   }
   void correctPoses() { check(fbr_pg_apply(c_.get()), "fbr_pg_apply"); }
 
+  /* visualizeGlobalMapThread's save block (:485-521) in three steps: build the global map from the
+   * keyframe store (params null: the reference's mode; wide = 1 is this project's extension for maps
+   * PCL's VoxelGrid refuses), read it back or install it as the registration map without leaving
+   * the device, and write the reference's files into an existing directory. */
+  fbr_gmap_result buildGlobalMap(const fbr_gmap_params* params = nullptr) {
+    fbr_gmap_result r{};
+    check(fbr_global_map_build(c_.get(), params, &r), "fbr_global_map_build");
+    return r;
+  }
+  void globalMap(std::vector<fbr_point_xyzi>* corner, std::vector<fbr_point_xyzi>* surf) {
+    int64_t nc = 0, ns = 0;
+    check(fbr_global_map_get(c_.get(), &nc, &ns, nullptr, nullptr), "fbr_global_map_get");
+    if (corner) corner->assign((size_t)nc, fbr_point_xyzi{});
+    if (surf) surf->assign((size_t)ns, fbr_point_xyzi{});
+    check(fbr_global_map_get(c_.get(), nullptr, nullptr, corner && nc ? corner->data() : nullptr,
+                             surf && ns ? surf->data() : nullptr),
+          "fbr_global_map_get");
+  }
+  void installGlobalMap() { check(fbr_global_map_install(c_.get()), "fbr_global_map_install"); }
+  void saveGlobalMap(const std::string& dir, bool cloud_global = false) {
+    check(fbr_global_map_save(c_.get(), dir.c_str(), cloud_global ? FBR_GMAP_SAVE_GLOBAL : 0), "fbr_global_map_save");
+  }
+
  private:
   Context& c_;
   double timeLastProcessing_ = -1.0;  // mapOptmization.h:135 (timeLastProcessing = -1)
