@@ -8,7 +8,7 @@
 // grid (float min / max box, leaf inverse, min_b, div_b, ijk) and widens the key to 64 bits:
 //   key = ijk0 + ijk1 * div0 + ijk2 * div0 * div1            (uint64)
 // Where PCL does not overflow the key equals PCL's, so the wide filter then emits VgGrid's voxels
-// (k_voxel.hip) in VgGrid's order.  Where PCL overflows there is no PCL output to reproduce: the
+// (fbr_vg_sort.h) in VgGrid's order.  Where PCL overflows there is no PCL output to reproduce: the
 // wide mode is the project's own extension.
 //
 // Limits, reported in status:

@@ -195,6 +195,9 @@ struct VgArgs {
 constexpr int32_t kVgErrLookback = 16;
 constexpr int64_t kVgLdsCap = 4096;  // segments up to this size sort entirely in LDS
 void launch_voxel_grid(hipStream_t s, const VgArgs& a);
+// fbr_selftest_radix_sort's in-place variants (3 .. 6) on the null stream: n device keys sorted in
+// place over their low nbits, vals = the source index of each position
+void launch_selftest_radix_ip(int variant, uint32_t* keys, uint32_t* vals, int n, int nbits);
 
 // Device scratch of the set-up paths (map VoxelGrid, kNN grid builds): one hipMalloc'd block per
 // context, grown when a call needs more (after draining the stream that used it) and carved by a
@@ -232,12 +235,15 @@ inline void arena_free(DevArena& a) {
   a = DevArena{};
 }
 
-// One large cloud on the whole device (rocprim stable radix sort); *d_nout gets the voxel count.
+// ---- A9 VoxelGrid of one large cloud on the whole device (k_voxel_large.hip; the sort, run
+// numbering and centroid it shares with the wide filter below: fbr_vg_runs.h) ----
+// rocprim stable radix sort; *d_nout gets the voxel count.
 // (Callers take it from knobs::vg_large_min() points on: below, the one-workgroup kernel is faster.)
 int voxel_grid_large(hipStream_t s, DevArena& ar, const float4* in, int64_t n, float leaf, int morton, int exact,
                      float4* out, int32_t* d_nout);
 
-// The wide VoxelGrid (k_gmap.hip): PCL's grid with 64-bit keys (fbr_gmap.h), for clouds PCL's own
+// ---- the wide VoxelGrid (k_gmap.hip) ----
+// PCL's grid with 64-bit keys (fbr_gmap.h), for clouds PCL's own
 // filter refuses.  The input is a concatenation described by KfSeg entries over a point pool and
 // never written out.
 struct KfSeg;
@@ -267,7 +273,8 @@ int gmap_compact_finite(hipStream_t s, DevArena& ar, const float4* in, int64_t n
 int voxel_grid_wide(hipStream_t s, DevArena& ar, const GmapSrc& src, float leaf, const GmapInfo* bounds,
                     const std::function<float4*(int64_t)>& alloc_out, GmapInfo* info);
 
-// Per-ring surf filter reading the projected cloud + label mask directly (no candidate copy).
+// ---- A9 per-ring surf VoxelGrid (k_voxel_ring.hip) ----
+// Reads the projected cloud + label mask directly (no candidate copy).
 struct VgRing {
   const float4* cloud;       // [B][H*W] projected cloud
   const int8_t* label;       // [B][H*W] cloudLabel
@@ -288,6 +295,7 @@ struct VgRing {
 };
 void launch_voxel_ring(hipStream_t s, const VgRing& a);
 
+// ---- per-job feature clouds (k_concat.hip) ----
 // Concatenate per-ring corner slots / per-ring surf DS outputs into per-job clouds (the
 // cornerCloud / surfaceCloud push_back order of featureExtraction.h:219,292).  ring_box (may be
 // null): per (job, ring) the corner then the surf points' {min xyz, max xyz} (kRingBox floats;

@@ -1335,7 +1335,7 @@ k_features(FeatArgs a) {
     }
     FBR_STAMP(7);
     // surf candidates (label <= 0 in [sp, ep], :279-284) are selected by the per-ring VoxelGrid
-    // straight from the label mask (k_voxel.hip, k_voxel_ring)
+    // straight from the label mask (k_voxel_ring.hip, k_voxel_ring)
     FBR_STAMP(8);
     }  // wave 0
     if constexpr (NWV > 1) __syncthreads();

@@ -9,37 +9,19 @@
 //                 does not depend on the order) and the count of points with a non-finite
 //                 coordinate; the host builds the grid from the six bounds (gmap_grid_init)
 //   k_gmw_keys    (key, concatenation index) per point; a non-finite point gets the drop key
-//   rocprim::radix_sort_pairs over the bits the grid needs (stable: a voxel's points stay in index order)
-//   k_gmw_heads, rocprim::exclusive_scan: voxel index of every run of equal keys
+//   vg_sorted_runs (fbr_vg_runs.h): the stable sort over the bits the grid needs (a voxel's points
+//                 stay in index order) and the voxel index of every run of equal keys
 //   k_gmw_emit    one centroid per run, its points re-transformed from the pool and summed in index
-//                 order: k_vgl_emit's arithmetic (k_voxel.hip), float sum / float count
+//                 order: vg_run_centroid, the arithmetic of k_voxel_large.hip's emit
 // HBM-bound: the pool is read twice in stream order (16 B per point) and once gathered by the
 // emit; keys and indices cost 12 B per point written, sorted and read.  No float atomics: two calls
 // return the same bytes.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "fbr_common.h"
 #include "fbr_gmap.h"
-#include "fbr_kernels.h"
-
-#include <algorithm>
-#include <cstring>
+#include "fbr_vg_runs.h"
 
 namespace fbr {
 
 namespace {
-
-__device__ __forceinline__ uint32_t gm_f2ord(float f) {  // order-preserving float -> uint
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float gm_ord2f(uint32_t u) {
-  const uint32_t b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
 
 // Point i of entry g of the concatenation.
 __device__ __forceinline__ float4 gm_point(const float4* __restrict__ pool, const KfSeg& g, int xform, int64_t i) {
@@ -78,18 +60,7 @@ __global__ void __launch_bounds__(256) k_gmw_bounds(const float4* __restrict__ p
     }
   }
   for (int o = 32; o > 0; o >>= 1) dropped += __shfl_xor(dropped, o);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    for (int o = 32; o > 0; o >>= 1) {
-      const float a = __shfl_xor(mn[d], o), b = __shfl_xor(mx[d], o);
-      mn[d] = (a < mn[d]) ? a : mn[d];
-      mx[d] = (mx[d] < b) ? b : mx[d];
-    }
-    if ((threadIdx.x & 63) == 0) {
-      atomicMin(&B->mm[d], gm_f2ord(mn[d]));
-      atomicMax(&B->mm[3 + d], gm_f2ord(mx[d]));
-    }
-  }
+  vg_merge_bounds(mn, mx, B->mm);
   if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&B->n_dropped, (unsigned long long)dropped);
 }
 
@@ -103,11 +74,6 @@ __global__ void __launch_bounds__(256) k_gmw_keys(const float4* __restrict__ poo
     keys[g.dst + i] = gm_finite(p) ? gmap_key(G, p.x, p.y, p.z) : gmap_drop_key(G);
     vals[g.dst + i] = (uint32_t)(g.dst + i);
   }
-}
-
-__global__ void __launch_bounds__(256) k_gmw_heads(const uint64_t* __restrict__ keys, int64_t n, uint32_t* __restrict__ head) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-    head[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 
 // The entry that holds concatenation index idx: the last one with dst <= idx (entries are in
@@ -128,25 +94,16 @@ k_gmw_emit(const float4* __restrict__ pool, const KfSeg* __restrict__ segs, int 
            const uint64_t* __restrict__ keys, const uint32_t* __restrict__ vals, const uint32_t* __restrict__ vox,
            float4* __restrict__ out, int64_t n_out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    if (!(i == 0 || keys[i] != keys[i - 1])) continue;
-    const uint64_t key = keys[i];
-    if (key == drop_key) continue;  // the run of dropped points (the last one)
+    if (!vg_run_head(keys, i)) continue;
+    if (keys[i] == drop_key) continue;  // the run of dropped points (the last one)
     const int64_t o = (int64_t)vox[i];
     if (o >= n_out) continue;  // cannot happen: the output holds every voxel before the dropped run
-    int sg = gm_find_seg(segs, nseg, (int64_t)vals[i], 0);
-    float4 c = gm_point(pool, segs[sg], xform, (int64_t)vals[i] - segs[sg].dst);
-    int64_t j = i + 1;
-    while (j < n && keys[j] == key) {
+    int sg = 0;  // the entry of the run's previous point
+    int64_t end;
+    out[o] = vg_run_centroid(keys, n, i, [&](int64_t j) {
       sg = gm_find_seg(segs, nseg, (int64_t)vals[j], sg);
-      const float4 p = gm_point(pool, segs[sg], xform, (int64_t)vals[j] - segs[sg].dst);
-      c.x += p.x;
-      c.y += p.y;
-      c.z += p.z;
-      c.w += p.w;
-      ++j;
-    }
-    const float cnt = (float)(j - i);
-    out[o] = make_float4(c.x / cnt, c.y / cnt, c.z / cnt, c.w / cnt);
+      return gm_point(pool, segs[sg], xform, (int64_t)vals[j] - segs[sg].dst);
+    }, &end);
   }
 }
 
@@ -189,7 +146,7 @@ int gmap_compact_finite(hipStream_t s, DevArena& ar, const float4* in, int64_t n
   uint32_t* pos = arena_take<uint32_t>(ar, 4 * N);
   void* tmp = arena_take<void>(ar, tb);
   if (!keep || !pos || !tmp) return FBR_ERR_HIP;
-  const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+  const int grid = vg_pass_grid(n);
   fbr_launch(k_gmw_finite, dim3(grid), dim3(256), 0, s, in, n, keep);
   if (rocprim::exclusive_scan(tmp, tb, keep, pos, 0u, N, rocprim::plus<uint32_t>(), s) != hipSuccess) return FBR_ERR_HIP;
   fbr_launch(k_gmw_compact, dim3(grid), dim3(256), 0, s, in, n, (const uint32_t*)keep, (const uint32_t*)pos, out, n_out);
@@ -214,8 +171,8 @@ int gmap_bounds(hipStream_t s, DevArena& ar, const GmapSrc& src, float leaf, Gma
   if (info->n_dropped >= src.n) return FBR_OK;  // no finite point: no grid
   float mn[3], mx[3];
   for (int d = 0; d < 3; ++d) {
-    mn[d] = gm_ord2f(h.mm[d]);
-    mx[d] = gm_ord2f(h.mm[3 + d]);
+    mn[d] = ord2f(h.mm[d]);
+    mx[d] = ord2f(h.mm[3 + d]);
   }
   gmap_grid_init(info->G, mn, mx, leaf);
   info->has_grid = 1;
@@ -237,45 +194,27 @@ int voxel_grid_wide(hipStream_t s, DevArena& ar, const GmapSrc& src, float leaf,
   if (src.n <= 0 || !I.has_grid) return FBR_OK;
   if (I.G.status != kGmapOk) return FBR_ERR_CAPACITY;
   const int64_t n = src.n;
-  const size_t N = (size_t)n;
-  const unsigned end_bit = (unsigned)I.G.nbits + 1;  // the voxel keys and the drop key above them
-  size_t tb_sort = 0, tb_scan = 0;
-  uint64_t* null64 = nullptr;
-  uint32_t* null32 = nullptr;
-  if (rocprim::radix_sort_pairs(nullptr, tb_sort, null64, null64, null32, null32, N, 0, end_bit, s) != hipSuccess ||
-      rocprim::exclusive_scan(nullptr, tb_scan, null32, null32, 0u, N, rocprim::plus<uint32_t>(), s) != hipSuccess)
-    return FBR_ERR_HIP;
-  const size_t tb = std::max<size_t>(std::max(tb_sort, tb_scan), 16);
-  if (arena_reserve(ar, 2 * arena_bytes(8 * N) + 4 * arena_bytes(4 * N) + arena_bytes(tb), s) != hipSuccess)
-    return FBR_ERR_HIP;
-  uint64_t* k0 = arena_take<uint64_t>(ar, 8 * N);
-  uint64_t* k1 = arena_take<uint64_t>(ar, 8 * N);
-  uint32_t* v0 = arena_take<uint32_t>(ar, 4 * N);
-  uint32_t* v1 = arena_take<uint32_t>(ar, 4 * N);
-  uint32_t* head = arena_take<uint32_t>(ar, 4 * N);
-  uint32_t* vox = arena_take<uint32_t>(ar, 4 * N);
-  void* tmp = arena_take<void>(ar, tb);
-  if (!k0 || !k1 || !v0 || !v1 || !head || !vox || !tmp) return FBR_ERR_HIP;  // arena sizing slip
-  const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  gm_launch_segs(k_gmw_keys, s, src, I.G, k0, v0);
-  if (rocprim::radix_sort_pairs(tmp, tb_sort, k0, k1, v0, v1, N, 0, end_bit, s) != hipSuccess) return FBR_ERR_HIP;
-  fbr_launch(k_gmw_heads, dim3(grid), dim3(256), 0, s, (const uint64_t*)k1, n, head);
-  if (rocprim::exclusive_scan(tmp, tb_scan, head, vox, 0u, N, rocprim::plus<uint32_t>(), s) != hipSuccess)
-    return FBR_ERR_HIP;
+  VgRuns<uint64_t> R;
+  // sorted over the voxel keys' bits and the drop key's above them
+  const int rc = vg_sorted_runs(s, ar, 0, n, (unsigned)I.G.nbits + 1, [&](VgRuns<uint64_t>& r) {
+    gm_launch_segs(k_gmw_keys, s, src, I.G, r.k0, r.v0);
+    return FBR_OK;
+  }, R);
+  if (rc) return rc;
   // runs of equal keys = vox[n - 1] + head[n - 1] (at most n <= INT32_MAX: the sum cannot wrap);
   // the dropped points, if any, are the last run
   uint32_t last[2] = {0, 0};
   if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(&last[0], vox + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipMemcpyAsync(&last[1], head + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(&last[0], R.vox + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipMemcpyAsync(&last[1], R.head + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return FBR_ERR_HIP;
   const int64_t n_out = (int64_t)last[0] + (int64_t)last[1] - (I.n_dropped > 0 ? 1 : 0);
   if (n_out < 0 || n_out > n) return FBR_ERR_HIP;
   float4* out = alloc_out(n_out);
   if (!out) return FBR_ERR_HIP;
-  fbr_launch(k_gmw_emit, dim3(grid), dim3(256), 0, s, src.pool, src.segs, src.nseg, src.xform, n, gmap_drop_key(I.G),
-             (const uint64_t*)k1, (const uint32_t*)v1, (const uint32_t*)vox, out, n_out);
+  fbr_launch(k_gmw_emit, dim3(vg_pass_grid(n)), dim3(256), 0, s, src.pool, src.segs, src.nseg, src.xform, n, gmap_drop_key(I.G),
+             (const uint64_t*)R.keys, (const uint32_t*)R.vals, (const uint32_t*)R.vox, out, n_out);
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return FBR_ERR_HIP;
   info->n_out = n_out;
   return FBR_OK;

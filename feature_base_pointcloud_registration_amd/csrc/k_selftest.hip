@@ -4,7 +4,8 @@
 // correctly rounded f32 sqrt and division (SSE sqrtss / divss), glibc atan2f
 // (imageProjection.cpp:605,618) and glibc sinf / cosf (pcl::getTransformation, LMOptimization
 // mapOptmization.h:1259-1264).  tests/test_gpu_parity.py feeds random operands through this
-// kernel and compares every output bit with the host.
+// kernel and compares every output bit with the host.  Also here: the selftests of the introsort
+// partition phase and of the wave-chunk radix sorts (fbr_vg_sort.h), and the bandwidth / VALU probes.
 #include <algorithm>
 
 #include "fbr_common.h"
@@ -12,6 +13,7 @@
 #include "fbr_sincosf.h"
 #include "fbr_introsort.h"
 #include "fbr_solvers.h"
+#include "fbr_vg_sort.h"
 
 namespace fbr {
 
@@ -127,7 +129,90 @@ __global__ void __launch_bounds__(512) k_selftest_isort3(uint32_t* k, uint32_t* 
   }
 }
 
+// ---- radix sort selftests (fbr_selftest_radix_sort): one workgroup sorts one array with the
+// product's configurations of the wave-chunk sorts ----
+// variant 0: vg_radix_sort<512, u16, 8, LDS> (per-ring filter), 1: vg_radix_sort<256, u16, 9, LDS>
+// (per-segment LDS kernel), 2: vg_radix_sort<1024, u32, 9, global> (global-scratch kernel),
+// 3: vg_radix_sort_inplace<1024, 18> (mapping DS), 4: the same with ballot-leader digit counts,
+// 5: round 3's rejected form (ballot-leader counts + wave-uniform early exits),
+// 6: vg_radix_sort_inplace<256, 16> (the small size class of the mapping DS).
+// (3 .. 6 run k_selftest_radix_ip, which k_voxel.hip keeps: see there.)
+template <int T, typename V, int MAXD, bool KV_LDS>
+__global__ void __launch_bounds__(T) k_selftest_radix(uint32_t* keys, uint32_t* vals, uint32_t* scratch, int n, int nbits) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NW = T / 64;
+  uint32_t* hist = (uint32_t*)smem;
+  uint32_t* wsum = hist + (NW + 1) * 512;
+  unsigned char* q = (unsigned char*)(wsum + NW);
+  q = smem + (((q - smem) + 15) & ~15);
+  uint32_t* kb[2];
+  V* vb[2];
+  if constexpr (KV_LDS) {
+    kb[0] = (uint32_t*)q;
+    kb[1] = kb[0] + n;
+    vb[0] = (V*)(kb[1] + n);
+    vb[1] = vb[0] + n;
+  } else {
+    kb[0] = scratch;
+    kb[1] = scratch + n;
+    vb[0] = (V*)(scratch + 2 * n);
+    vb[1] = (V*)(scratch + 3 * n);
+  }
+  for (int i = threadIdx.x; i < n; i += T) {
+    kb[0][i] = keys[i];
+    vb[0][i] = (V)i;
+  }
+  __syncthreads();
+  const int cur = vg_radix_sort<T, V, MAXD, KV_LDS>(kb, vb, n, nbits, hist, wsum);
+  for (int i = threadIdx.x; i < n; i += T) {
+    keys[i] = kb[cur][i];
+    vals[i] = (uint32_t)vb[cur][i];
+  }
+}
+
 }  // namespace fbr
+
+// Diagnostic entry point (tests/test_gpu_parity.py): sort n keys (low nbits significant) with one of
+// the product's radix sort configurations; keys_inout gets the sorted keys, perm the source index of
+// each sorted position.
+extern "C" int fbr_selftest_radix_sort(int64_t n, int nbits, int variant, uint32_t* keys_inout, uint32_t* perm) {
+  using namespace fbr;
+  const int64_t lcap[7] = {4096, 4096, 1 << 20, 1024 * kVgIpKpl, 1024 * kVgIpKpl, 1024 * kVgIpKpl,
+                           kVgIpSmallT * kVgIpSmallKpl};
+  if (n < 0 || variant < 0 || variant > 6 || n > lcap[variant] || nbits < 1 || nbits > 32 || (n && (!keys_inout || !perm)))
+    return FBR_ERR_INVALID_ARG;
+  if (n == 0) return FBR_OK;
+  uint32_t *dk = nullptr, *dv = nullptr, *ds = nullptr;
+  int rc = FBR_OK;
+  if (hipMalloc(&dk, 4 * n) != hipSuccess || hipMalloc(&dv, 4 * n) != hipSuccess || hipMalloc(&ds, 16 * n) != hipSuccess ||
+      hipMemcpy(dk, keys_inout, 4 * n, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else {
+    const int nn = (int)n;
+    auto hdr = [](int T) { return (((size_t)(T / 64 + 1) * 512 + T / 64) * 4 + 15) & ~(size_t)15; };
+    switch (variant) {
+      case 0:
+        hipLaunchKernelGGL((k_selftest_radix<512, uint16_t, 8, true>), dim3(1), dim3(512), hdr(512) + (size_t)n * 12, 0,
+                           dk, dv, ds, nn, nbits);
+        break;
+      case 1:
+        hipLaunchKernelGGL((k_selftest_radix<256, uint16_t, 9, true>), dim3(1), dim3(256), hdr(256) + (size_t)n * 12, 0,
+                           dk, dv, ds, nn, nbits);
+        break;
+      case 2:
+        hipLaunchKernelGGL((k_selftest_radix<1024, uint32_t, 9, false>), dim3(1), dim3(1024), hdr(1024), 0, dk, dv, ds,
+                           nn, nbits);
+        break;
+      default:  // 3 .. 6: the in-place sort, whose selftest kernel stands with its product callers
+        launch_selftest_radix_ip(variant, dk, dv, nn, nbits);
+    }
+    if (hipGetLastError() != hipSuccess || hipMemcpy(keys_inout, dk, 4 * n, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(perm, dv, 4 * n, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = FBR_ERR_HIP;
+  }
+  for (void* q : {(void*)dk, (void*)dv, (void*)ds}) (void)hipFree(q);
+  return rc;
+}
 
 extern "C" int fbr_selftest_voxel_order(int64_t n, const uint32_t* keys, int lds, uint32_t* perm) {
   if (n < 0 || n > (int64_t)INT32_MAX / 4 || (n && (!keys || !perm)) || (lds == 1 && n > fbr::kIsortLdsCap) ||

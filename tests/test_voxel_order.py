@@ -193,7 +193,7 @@ def _morton(x, y, z):
                          ids=["ring-lds-512", "segment-lds-256", "global-1024", "inplace-atomic", "inplace-leader",
                               "inplace-leader-r03"])
 def test_voxel_radix_sorts_are_stable_sorts(variant, cap, nw):
-    """Every wave-chunk radix sort configuration of k_voxel.hip (fbr_selftest_radix_sort) against a
+    """Every wave-chunk radix sort configuration of fbr_vg_sort.h (fbr_selftest_radix_sort) against a
     host stable sort, on every chunk fill including full ones and on long equal-digit runs.  Variant
     4 is round 3's ballot-leader digit count in the in-place sort, 5 the exact form round 3 reverted
     (the leader count plus a wave-uniform early exit in both loops)."""
