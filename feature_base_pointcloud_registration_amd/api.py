@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "fbr_destroy", "fbr_set_map", "fbr_get_map", "fbr_project", "fbr_extract_features",
     "fbr_register", "fbr_register_trace", "fbr_process_scan", "fbr_reset_stream",
     "fbr_process_batch", "fbr_ingest_bytes", "fbr_debug_counters", "fbr_map_grid_info", "fbr_batch_stage", "fbr_batch_launch", "fbr_batch_wait",
-    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
+    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_diag_batch_cloud", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
     "fbr_voxel_grid", "fbr_affine_from_pose", "fbr_pose_from_affine", "fbr_selftest_math", "fbr_selftest_eigen6", "fbr_selftest_eig_certified", "fbr_selftest_voxel_order", "fbr_selftest_radix_sort",
     "fbr_load_map", "fbr_pcd_read", "fbr_pcd_write_ascii", "fbr_pcd_write_binary",
     "fbr_msg_to_points", "fbr_points_to_msg_data", "fbr_project_msg", "fbr_process_msg",
@@ -893,6 +893,17 @@ class Context:
         f = lib().fbr_diag_ring_filter
         f.restype, f.argtypes = ctypes.c_int, [_VP, ctypes.c_int]
         _check(f(self._h, int(kernel)), "fbr_diag_ring_filter")
+
+    def diag_batch_cloud(self, force_wide=-1):
+        """Diagnostic: force_wide 1 keeps the float4 projected cloud in the batch launches that
+        would take 12-B (x, y, z) records, 0 restores the default, -1 leaves the switch
+        (fbr_diag_batch_cloud).  Returns the record size of the latest batch launch's cloud: 12, 16,
+        or 0 before any launch."""
+        f = lib().fbr_diag_batch_cloud
+        f.restype, f.argtypes = ctypes.c_int, [_VP, ctypes.c_int, _VP]
+        n = _I32()
+        _check(f(self._h, int(force_wide), ctypes.byref(n)), "fbr_diag_batch_cloud")
+        return n.value
 
     def diag_force_capacity_error(self, job):
         """Diagnostic: batch job `job` of the following launches is reported as over the feature

@@ -302,6 +302,17 @@ extern "C" int fbr_diag_ring_filter(fbr_ctx* c, int kernel) {
   return FBR_OK;
 }
 
+// Diagnostic (A/B and tests): force_wide 1 keeps the float4 projected cloud in the batch launches
+// that would take the 12-B records (fbr_stages.hip, batch_cloud12), 0 restores the default, < 0
+// leaves the switch as it is; *point_bytes (may be null) receives the record size of the last batch
+// launch's cloud: 12, 16, or 0 before the first launch.
+extern "C" int fbr_diag_batch_cloud(fbr_ctx* c, int force_wide, int32_t* point_bytes) {
+  if (!c) return FBR_ERR_INVALID_ARG;
+  if (force_wide >= 0) c->diag_wide_cloud = force_wide != 0;
+  if (point_bytes) *point_bytes = c->last_cloud_bytes;
+  return FBR_OK;
+}
+
 // Diagnostic: batch job `job` of the following launches is treated as over the feature capacity
 // (as if k_features had flagged it), so the tests can check how fbr_batch_results and the exported
 // records report such a job (no valid scan reaches the capacity: a ring holds at most W points);

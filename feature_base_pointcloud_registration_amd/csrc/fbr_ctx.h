@@ -495,6 +495,8 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   // ---- diagnostics (fbr_api.hip) ----
   int diag_err_job = -1;      // diagnostic (fbr_diag_force_capacity_error): batch job flagged over capacity
   int diag_ring_filter = -1;  // diagnostic (fbr_diag_ring_filter): per-ring surf filter kernel, -1 = by size
+  bool diag_wide_cloud = false;  // diagnostic (fbr_diag_batch_cloud): batch launches keep the float4 cloud
+  int last_cloud_bytes = 0;      // record size of the last batch launch's projected cloud (12 or 16; 0: none yet)
   Dev<unsigned long long> d_feat_stamps;  // diagnostic builds (FBR_FEAT_STAMPS) only
   Dev<uint32_t> d_feat_paths;             // tests (fbr_diag_feature_paths): FeatArgs::paths [Bwork][H]
 };

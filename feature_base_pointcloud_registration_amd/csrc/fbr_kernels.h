@@ -104,16 +104,26 @@ struct DeskArgs {
   const fbr_deskew_table* table;
   int32_t* rowmin;
 };
+// The 12-B cloud record of the batch front end (x, y, z; 4-B aligned), beside float4 in the same
+// allocation: a job's records start at its float4 base (cloud + job * HW) and are packed 12 B apart.
+// A launch takes it when nothing reads a fourth word (fbr_stages.hip, batch_cloud12): its clouds'
+// w is 0 throughout, and the readers put that constant back where a float4 leaves them.
+struct Pt3 {
+  float x, y, z;
+};
+static_assert(sizeof(Pt3) == 12 && alignof(Pt3) == 4, "Pt3 is three packed floats");
 // choff: [B][H][ceil(W / 32)] scratch (claimed cells of a row before each compaction tile)
+// c12: the cloud is written as Pt3 records (pk launches only)
 void launch_extract(hipStream_t s, const fbr_point_xyzirt* pts, int64_t nmax, int32_t* owner, int B, int H,
                     int W, int32_t* rowcnt, int32_t* choff, float4* cloud, int32_t* col, float* range,
                     int32_t* start_ring, int32_t* end_ring, int32_t* nvalid, const DeskArgs& desk,
-                    const float4* pk, const OwnerTag& ot);
+                    const float4* pk, const OwnerTag& ot, bool c12 = false);
 
 // ---- A6-A8 (k_features.hip) ----
 struct FeatArgs {
   int B, H, W;
   const float4* cloud;
+  int c12 = 0;           // 1: the cloud holds Pt3 records from each job's float4 base (wave-uniform)
   const int32_t* col;
   const float* range;
   const int32_t* start_ring;
@@ -292,7 +302,11 @@ struct VgRing {
                              // per ring (fbr_diag_ring_filter: tests compare the two)
   int exact;                 // 1: PCL's point order inside voxels (std::sort's, fbr_introsort.h)
   unsigned long long* stamps;  // diagnostic builds (FBR_VR_STAMPS) only: [B*H][12]
+  int c12 = 0;               // 1: the cloud holds Pt3 records (four-wave kernel only: vr_takes_four_waves)
 };
+// Whether the launch runs the four-wave kernel (k_voxel_ring_q), the only reader of Pt3 clouds:
+// default order, chosen by size or forced, no diagnostic phase cut.
+bool vr_takes_four_waves(const VgRing& a);
 void launch_voxel_ring(hipStream_t s, const VgRing& a);
 
 // ---- per-job feature clouds (k_concat.hip) ----

@@ -187,6 +187,29 @@ namespace internal {
 // reference's stage objects keep between scans is carried between calls).
 Sub single_sub(fbr_ctx* c) { return Sub{0, 1, 0, c->stream, true}; }
 
+// The per-ring surf filter's launch selection of a sub-batch (the fields launch_voxel_ring decides by).
+static VgRing ring_filter_choice(fbr_ctx* c, const Sub& sb) {
+  VgRing v{};
+  v.B = sb.B;
+  v.H = c->H;
+  v.cap = c->W;
+  v.dbg = knobs::vr_dbg();
+  v.exact = c->P.exact_voxel_order ? 1 : 0;
+  v.kernel = c->diag_ring_filter;
+  return v;
+}
+
+// Whether a sub-batch's projected cloud is Pt3 records (fbr_kernels.h).  Only where every reader of
+// the launch takes them and the fourth word is the constant 0: 16-B scan records (so no deskew, no
+// intensity), not stream mode (fbr_project / fbr_extract_features hand the float4 cloud out), and
+// the four-wave per-ring filter (the exact-order and 512-thread kernels read float4).  stage_project
+// and stage_features of one launch both decide by this, from state that does not change between them.
+static bool batch_cloud12(fbr_ctx* c, const Sub& sb) {
+  if (sb.stream_mode || c->diag_wide_cloud) return false;
+  if ((c->desk_any && !c->no_time_call) || !c->staged_pk) return false;  // (stage_project's pk)
+  return vr_takes_four_waves(ring_filter_choice(c, sb));
+}
+
 int stage_project(fbr_ctx* c, const Sub& sb) {
   const int64_t j0 = sb.j0, i0 = sb.in0;
   DeskArgs desk{nullptr, nullptr, nullptr};
@@ -199,13 +222,15 @@ int stage_project(fbr_ctx* c, const Sub& sb) {
   OwnerTag ot;
   const int trc = next_owner_tag(c, &ot);
   if (trc) return trc;
+  const bool c12 = pk && batch_cloud12(c, sb);
+  if (!sb.stream_mode) c->last_cloud_bytes = c12 ? (int)sizeof(Pt3) : (int)sizeof(float4);
   TIMED_ON(c, sb.st, "project", launch_project(sb.st, c->d_pts + i0 * c->NMAX, c->d_nin + i0, c->NMAX, sb.B, c->H,
                                                c->W, owner, c->d_err + j0, sb.stream_mode ? c->single_n : -1, pk, ot));
   TIMED_ON(c, sb.st, "extract",
            launch_extract(sb.st, c->d_pts + i0 * c->NMAX, c->NMAX, owner, sb.B, c->H, c->W, c->d_rowcnt + j0 * c->H,
                           c->d_choff + j0 * c->H * (c->W / 32 + 1),
                           c->d_cloud + j0 * c->HW, c->d_col + j0 * c->HW, c->d_range + j0 * c->HW,
-                          c->d_start + j0 * c->H, c->d_end + j0 * c->H, c->d_nvalid + j0, desk, pk, ot));
+                          c->d_start + j0 * c->H, c->d_end + j0 * c->H, c->d_nvalid + j0, desk, pk, ot, c12));
   return FBR_OK;
 }
 
@@ -219,6 +244,7 @@ int stage_features(fbr_ctx* c, const Sub& sb, bool stream_mode, bool err_clear, 
   a.H = c->H;
   a.W = c->W;
   a.cloud = c->d_cloud + j0 * HW;
+  a.c12 = !stream_mode && batch_cloud12(c, sb) ? 1 : 0;
   a.col = c->d_col + j0 * HW;
   a.range = c->d_range + j0 * HW;
   a.start_ring = c->d_start + j0 * H;
@@ -267,6 +293,7 @@ int stage_features(fbr_ctx* c, const Sub& sb, bool stream_mode, bool err_clear, 
   v.exact = c->P.exact_voxel_order ? 1 : 0;
   v.stamps = a.stamps;
   v.kernel = c->diag_ring_filter;
+  v.c12 = a.c12;
   TIMED_ON(c, sb.st, "voxel_ring", launch_voxel_ring(sb.st, v));
   TIMED_ON(c, sb.st, "concat",
            launch_concat(sb.st, sb.B, c->H, c->W, a.corner_slot, a.corner_cnt, v.out, v.cnt_out,

@@ -133,6 +133,16 @@ __device__ __forceinline__ float curv_at(const FeatLds& S, int li, int slen) {
   return (k >= 0 && k < slen) ? S.scurv[k] : S.gcurv[li];
 }
 
+// A picked corner's point: the float4 record, or with FeatArgs::c12 (wave-uniform) the Pt3 record at
+// the same index from the job's base and the w = 0 such a launch's float4 cloud would hold.
+__device__ __forceinline__ float4 cloud_point(const float4* CL, int c12, int i) {
+  if (c12) {
+    const Pt3 p = reinterpret_cast<const Pt3*>(CL)[i];
+    return make_float4(p.x, p.y, p.z, 0.0f);
+  }
+  return CL[i];
+}
+
 // Sequential walks (the reference loops verbatim) over S.seg[0..m] (seg[m] = the unsorted ep entry).
 __device__ __forceinline__ void serial_walks(const FeatLds& S, int slen, const SmoothEntry* ent, const FeatArgs& a, int job, int m,
                              const float4* CL, float4* corner_out, int& corner_cnt) {
@@ -145,7 +155,7 @@ __device__ __forceinline__ void serial_walks(const FeatLds& S, int slen, const S
       largestPickedNum++;
       if (largestPickedNum <= kCornerPerSeg) {
         S.labpos.set_serial(li);
-        corner_out[corner_cnt++] = CL[ind];
+        corner_out[corner_cnt++] = cloud_point(CL, a.c12, ind);
       } else {
         break;
       }
@@ -538,7 +548,7 @@ __device__ __forceinline__ bool stale_walks_fast(const FeatLds& S, int slen, con
   if (lv) atomicOr((unsigned long long*)&S.labneg.w[myw], (unsigned long long)lv);
   if (myw < S.nw) S.picked.w[myw] = pv;
   wsync();
-  for (int t = lane; t < nc; t += 64) corner_out[corner_cnt + t] = CL[tlist[t]];
+  for (int t = lane; t < nc; t += 64) corner_out[corner_cnt + t] = cloud_point(CL, a.c12, tlist[t]);
   corner_cnt += nc;
   wsync();
   return true;
@@ -1184,7 +1194,7 @@ k_features(FeatArgs a) {
         const uint64_t mk = __ballot(acc);
         const int pos = taken + __popcll(mk & ((1ull << lane) - 1ull));
         if (acc && pos < kCornerPerSeg) {
-          corner_out[corner_cnt + pos] = CL[sp + u];
+          corner_out[corner_cnt + pos] = cloud_point(CL, a.c12, sp + u);
           const int li = sp + u - S.wlo;
           const uint32_t c = S.cm[u];
           atomicOr((unsigned long long*)&S.labpos.w[li >> 6], 1ull << (li & 63));

@@ -234,7 +234,9 @@ __device__ __forceinline__ float4 deskew_point(const fbr_point_xyzirt& q, const 
 // LDS (dynamic): xyzi [HB*CG] float4, owners [HB*CG] int32, and with deskew the raw ranges
 // [HB*CG] float (without deskew the staged point is the raw point and the range is recomputed
 // from it at the write, same expression, same bits): 20 KB per 1024-cell tile.
-template <bool kDesk, bool kPk = false>
+// k12 (kPk launches whose readers take Pt3, fbr_kernels.h): the cloud is written as 12-B records, three
+// dwords at rowoff + rank from the job's float4 base; col and range as in every other instance.
+template <bool kDesk, bool kPk = false, bool k12 = false>
 __global__ void __launch_bounds__(256)
 k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ pk, int64_t nmax, int32_t* __restrict__ owner,
           const int32_t* __restrict__ rowcnt, const int32_t* __restrict__ choff, int B, int H, int W, int HB, int CG,
@@ -404,7 +406,8 @@ k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ p
     if (v) {
       const int dst = rowoff[r] + rank;
       const float4 p = pxyz[k];
-      C[dst] = p;
+      if constexpr (k12) reinterpret_cast<Pt3*>(C)[dst] = Pt3{p.x, p.y, p.z};
+      else C[dst] = p;
       CI[dst] = c0 + c;
       R[dst] = kDesk ? prng[k] : sqrt_rn(p.x * p.x + p.y * p.y + p.z * p.z);
     }
@@ -523,7 +526,7 @@ void launch_project(hipStream_t s, const fbr_point_xyzirt* pts, const int64_t* n
 void launch_extract(hipStream_t s, const fbr_point_xyzirt* pts, int64_t nmax, int32_t* owner, int B, int H,
                     int W, int32_t* rowcnt, int32_t* choff, float4* cloud, int32_t* col, float* range,
                     int32_t* start_ring, int32_t* end_ring, int32_t* nvalid, const DeskArgs& desk, const float4* pk,
-                    const OwnerTag& ot) {
+                    const OwnerTag& ot, bool c12) {
   const CompactTile T = compact_tile(H, knobs::compact_cells());
   fbr_launch(k_rowcount, dim3(H, B), dim3(64), 0, s, owner, H, W, T.cg, rowcnt, desk.mode ? desk.rowmin : nullptr,
              choff, ot);
@@ -534,6 +537,9 @@ void launch_extract(hipStream_t s, const fbr_point_xyzirt* pts, int64_t nmax, in
   if (desk.mode)
     fbr_launch(k_compact<true>, grid, dim3(256), (uint32_t)(cells * 24), s, pts, pk, nmax, owner, rowcnt, choff, B,
                H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);
+  else if (pk && c12)
+    fbr_launch((k_compact<false, true, true>), grid, dim3(256), (uint32_t)(cells * 20), s, pts, pk, nmax, owner, rowcnt,
+               choff, B, H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);
   else if (pk)
     fbr_launch(k_compact<false, true>, grid, dim3(256), (uint32_t)(cells * 20), s, pts, pk, nmax, owner, rowcnt,
                choff, B, H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);

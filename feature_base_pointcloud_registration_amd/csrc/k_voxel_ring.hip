@@ -388,9 +388,16 @@ __device__ int vr_sort_runs(const uint32_t* kb, int R, uint16_t* sid, uint16_t* 
 // allocation is sensitive to the attribute's spelling: (8) on both instances or (8, 8) here gives
 // 64 VGPRs; a separate kernel per KQ or (8, 8) with another maximum for KQ = 16 missed the target
 // (69 VGPRs, 7 waves) on this compiler.
-template <int KQ>  // steps of 64 points per wave: 4 * 64 * KQ >= the ring capacity
+// PT = Pt3 (VgRing::c12, batch launches whose clouds carry no fourth word): both reads of a point
+// fetch 12 B, and the emit and the overflow copy write the w = 0 that such a cloud's float4 holds
+// (a sum of +0.0f over cnt >= 1 is +0.0f): the same bits out.
+__device__ __forceinline__ float4 vr_f4(const float4& p) { return p; }
+__device__ __forceinline__ float4 vr_f4(const Pt3& p) { return make_float4(p.x, p.y, p.z, 0.0f); }
+
+template <int KQ, typename PT = float4>  // steps of 64 points per wave: 4 * 64 * KQ >= the ring capacity
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(KQ <= 8 ? 8 : 1, KQ <= 8 ? 8 : 10)))
 k_voxel_ring_q(VgRing A) {
+  constexpr bool k12 = std::is_same<PT, Pt3>::value;
   constexpr int NW = 4;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ float mmx[NW][6];
@@ -418,7 +425,7 @@ k_voxel_ring_q(VgRing A) {
     for (int j = 0; j < 6; ++j) in |= sp6[j] < ep6[j] && k >= sp6[j] && k <= ep6[j];
     return in;
   };
-  const float4* CL = A.cloud + (int64_t)job * A.HW + s;
+  const PT* CL = reinterpret_cast<const PT*>(A.cloud + (int64_t)job * A.HW) + s;
   const int8_t* LB = A.label + (int64_t)job * A.HW + s;
   const int len = min(e - s, (int)A.cap);
   const uint64_t lt = (1ull << lane) - 1ull;
@@ -428,7 +435,7 @@ k_voxel_ring_q(VgRing A) {
   // Every label and point load of the wave is issued before any is used: loads of a clamped index
   // (no branch), then an empty asm that takes all the values.  Without it the compiler sank each
   // point load under its label test, a chain of 2 * KQ dependent round trips per wave.
-  float4 pt[KQ];
+  PT pt[KQ];
   bool cd[KQ];
   int lb[KQ];
 #pragma unroll
@@ -504,9 +511,9 @@ k_voxel_ring_q(VgRing A) {
     const int pos = base + __popcll(b & lt);
     if (cd[u]) {
       if (G.overflow) {  // PCL: "Leaf size is too small" -> output = input, in index order
-        out[pos] = CL[q0 + 64 * u + lane];  // re-read: only x, y, z stay live from pass A
+        out[pos] = vr_f4(CL[q0 + 64 * u + lane]);  // re-read: only x, y, z stay live from pass A
       } else {
-        kb[pos] = G.key(pt[u]);
+        kb[pos] = G.key(vr_f4(pt[u]));
         off[pos] = (uint16_t)(q0 + 64 * u + lane);
       }
     }
@@ -605,26 +612,27 @@ k_voxel_ring_q(VgRing A) {
       const int rid = sid[g];
       const int ta = rst[rid], tb = rst[rid + 1];
       for (int t = ta; t < tb; t += 8) {  // a run's points, 8 gathers in flight
-        float4 pp[8];
+        PT pp[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) pp[u] = CL[off[min(t + u, tb - 1)]];
 #pragma unroll
         for (int u = 0; u < 8; ++u)
           if (t + u < tb) {
             if (cnt == 0) {
-              c = pp[u];
+              c = vr_f4(pp[u]);
             } else {
               c.x += pp[u].x;
               c.y += pp[u].y;
               c.z += pp[u].z;
-              c.w += pp[u].w;
+              if constexpr (!k12) c.w += pp[u].w;
             }
             ++cnt;
           }
       }
     }
     const float fc = (float)cnt;
-    out[vv] = make_float4(c.x / fc, c.y / fc, c.z / fc, c.w / fc);
+    if constexpr (k12) out[vv] = make_float4(c.x / fc, c.y / fc, c.z / fc, 0.0f);
+    else out[vv] = make_float4(c.x / fc, c.y / fc, c.z / fc, c.w / fc);
   }
   if (tid == 0) A.cnt_out[slot] = V;
 }
@@ -633,6 +641,10 @@ k_voxel_ring_q(VgRing A) {
 // rings (single scans), where the 512-thread kernel finishes a ring sooner (C2 single scan: 19.8 vs
 // 34.3 us, profiles/r04u_latency_scan_timeline.txt) and the chip has room for the extra threads.
 bool vr_four_waves(int nseg) { return nseg > 256; }
+
+bool vr_takes_four_waves(const VgRing& a) {
+  return !a.exact && (a.kernel < 0 ? vr_four_waves(a.B * a.H) : a.kernel == 2) && a.dbg == 0 && a.cap <= 4096;
+}
 
 size_t voxel_ring_lds_bytes(const VgRing& a, int threads, int kpt) {
   const int nw = threads / 64;
@@ -658,10 +670,15 @@ void launch_voxel_ring(hipStream_t s, const VgRing& a) {
   };
   if (a.exact) {
     go(std::true_type{});
-  } else if ((a.kernel < 0 ? vr_four_waves(nseg) : a.kernel == 2) && a.dbg == 0 && a.cap <= 4096) {
+  } else if (vr_takes_four_waves(a)) {
     const size_t lds = (((size_t)a.cap + 1) * 4 + (size_t)a.cap * 2 + ((size_t)a.cap + 1) * 2 + 15) & ~(size_t)15;
-    if (a.cap <= 4 * 64 * 8) fbr_launch(k_voxel_ring_q<8>, dim3(nseg), dim3(256), lds, s, a);
-    else fbr_launch(k_voxel_ring_q<16>, dim3(nseg), dim3(256), lds, s, a);
+    if (a.c12) {
+      if (a.cap <= 4 * 64 * 8) fbr_launch((k_voxel_ring_q<8, Pt3>), dim3(nseg), dim3(256), lds, s, a);
+      else fbr_launch((k_voxel_ring_q<16, Pt3>), dim3(nseg), dim3(256), lds, s, a);
+    } else {
+      if (a.cap <= 4 * 64 * 8) fbr_launch(k_voxel_ring_q<8>, dim3(nseg), dim3(256), lds, s, a);
+      else fbr_launch(k_voxel_ring_q<16>, dim3(nseg), dim3(256), lds, s, a);
+    }
   } else {
     go(std::false_type{});
   }

@@ -812,6 +812,12 @@ int fbr_batch_set_full_masks(fbr_ctx* ctx, int on);
  * launch ran with full masks; FBR_ERR_CAPACITY (with *n_out set) if cap < *n_out.  Waits for the
  * launches in flight. */
 int fbr_batch_labels(fbr_ctx* ctx, int job, int8_t* label, int64_t cap, int64_t* n_out);
+/* Diagnostic (A/B and tests).  A batch launch staged from 16-B records, without deskew and with the
+ * default-order four-wave ring filter, keeps its projected cloud as 12-B (x, y, z) records; every
+ * other launch keeps 16-B float4.  Results are the same either way.  force_wide 1: the following
+ * launches keep float4; 0: the default; < 0: the switch is left as it is.  *point_bytes (may be
+ * NULL) receives the record size of the latest batch launch's cloud: 12, 16, or 0 before any. */
+int fbr_diag_batch_cloud(fbr_ctx* ctx, int force_wide, int32_t* point_bytes);
 /* Enqueue (on the ctx stream, after every launch in flight) a copy of the latest launch's per-job
  * pose records {pose[6] f32, iterations i32, status i32} = 32 B/job into `device_dst` (device
  * memory of the ctx's device, [n_jobs][8] x 4 B) — the payload of the cross-GPU pose all-gather. */
