@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = [
     "fbr_destroy", "fbr_set_map", "fbr_get_map", "fbr_project", "fbr_extract_features",
     "fbr_register", "fbr_register_trace", "fbr_process_scan", "fbr_reset_stream",
     "fbr_process_batch", "fbr_ingest_bytes", "fbr_debug_counters", "fbr_map_grid_info", "fbr_batch_stage", "fbr_batch_launch", "fbr_batch_wait",
-    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_diag_batch_cloud", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
+    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_diag_batch_cloud", "fbr_diag_knn_last", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
     "fbr_voxel_grid", "fbr_affine_from_pose", "fbr_pose_from_affine", "fbr_selftest_math", "fbr_selftest_eigen6", "fbr_selftest_eig_certified", "fbr_selftest_voxel_order", "fbr_selftest_radix_sort",
     "fbr_load_map", "fbr_pcd_read", "fbr_pcd_write_ascii", "fbr_pcd_write_binary",
     "fbr_msg_to_points", "fbr_points_to_msg_data", "fbr_project_msg", "fbr_process_msg",
@@ -904,6 +904,26 @@ class Context:
         n = _I32()
         _check(f(self._h, int(force_wide), ctypes.byref(n)), "fbr_diag_batch_cloud")
         return n.value
+
+    def diag_knn_last(self):
+        """Diagnostic: the last neighbour search of the latest single-scan registration on this
+        context (fbr_diag_knn_last).  Returns a dict: n_corner / n_surf (down-sampled query counts),
+        queries (n, 3) float32 map-frame positions as that pass computed them (corner queries
+        first), nbr (n, 5) int32 map indices into get_map()'s clouds in (d2, index) order (-1 five
+        times: no correspondence), desc (iterations, r, rx, flat, sparse, lpq, fused, tiles of the
+        kernel that ran the pass)."""
+        f = lib().fbr_diag_knn_last
+        f.restype, f.argtypes = ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, _VP]
+        nc, ns = _I32(), _I32()
+        desc = (_I32 * 8)()
+        _check(f(self._h, ctypes.byref(nc), ctypes.byref(ns), None, None, 0, desc), "fbr_diag_knn_last")
+        n = nc.value + ns.value
+        q = np.zeros((max(n, 1), 3), np.float32)
+        nbr = np.zeros((max(n, 1), 5), np.int32)
+        _check(f(self._h, ctypes.byref(nc), ctypes.byref(ns), ptr(q), ptr(nbr), max(n, 1), desc), "fbr_diag_knn_last")
+        names = ("iterations", "r", "rx", "flat", "sparse", "lpq", "fused", "tiles")
+        return dict(n_corner=nc.value, n_surf=ns.value, queries=q[:n].copy(), nbr=nbr[:n].copy(),
+                    desc={k: int(v) for k, v in zip(names, desc)})
 
     def diag_force_capacity_error(self, job):
         """Diagnostic: batch job `job` of the following launches is reported as over the feature

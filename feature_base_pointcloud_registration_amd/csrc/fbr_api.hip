@@ -191,7 +191,7 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
               dalloc(c->d_feat_scratch, Bw * H * feat_slot_bytes(c->W)) ||
               dalloc(c->h_iter_flags, kMaxSub * (std::max(1, p->max_iterations) + 1)) ||
               hipHostGetDevicePointer((void**)&c->d_iter_flags, c->h_iter_flags, 0) != hipSuccess || dalloc(c->d_pose_out, Bw * 6) ||
-              dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6) ||
+              dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6 + 12) ||
               dalloc(c->d_desk_mode, B) || dalloc(c->d_rowmin, Bw * H) || dalloc(c->d_result, B) ||
               dalloc(c->d_choff, Bw * H * (c->W / 32 + 1)) ||
               dalloc(c->h_result, B) || dalloc(c->h_scan, c->NMAX) || dalloc(c->h_nin, 1) || dalloc(c->h_crop, 2) ||
@@ -203,6 +203,7 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
     return FBR_ERR_HIP;
   }
   c->d_pts = c->d_pts_own;
+  c->knn_desc.assign((size_t)std::max(1, p->max_iterations), KnnLaunchDesc{});
   std::memset(c->h_iter_flags, 0, sizeof(unsigned long long) * kMaxSub * (std::max(1, p->max_iterations) + 1));
   std::memset(c->h_direct, 0, sizeof(JobResult));
   if (hipMemset(c->d_sstream, 0, sizeof(StreamState)) != hipSuccess ||
@@ -310,6 +311,71 @@ extern "C" int fbr_diag_batch_cloud(fbr_ctx* c, int force_wide, int32_t* point_b
   if (!c) return FBR_ERR_INVALID_ARG;
   if (force_wide >= 0) c->diag_wide_cloud = force_wide != 0;
   if (point_bytes) *point_bytes = c->last_cloud_bytes;
+  return FBR_OK;
+}
+
+// Diagnostic (tests): the last kNN pass of the latest single-scan registration, decoded on the host
+// from what the device keeps anyway: the down-sampled clouds, the work items, GnArgs::nbr and the
+// transform k_gn_solve kept (GnArgs::knn_T).  The positions restate gn_knn_block's
+// pointAssociateToMap in float; the library is built without contraction, so they are its bits.
+extern "C" int fbr_diag_knn_last(fbr_ctx* c, int32_t* n_corner, int32_t* n_surf, float* queries, int32_t* nbr,
+                                 int64_t cap, fbr_knn_desc* desc) {
+  if (!c || cap < 0 || (cap && (!queries || !nbr))) return FBR_ERR_INVALID_ARG;
+  if (!c->knn_last_valid) return FBR_ERR_STATE;
+  CK(enter(c));
+  CK(fbr_sync(c->stream));
+  GnState g;
+  int32_t ncs[2], range[2];
+  CK(fbr_memcpy_sync(&g, c->d_gn, sizeof(g), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(&ncs[0], c->d_ncds, sizeof(int32_t), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(&ncs[1], c->d_nsds, sizeof(int32_t), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(range, c->d_item_range, sizeof(range), hipMemcpyDeviceToHost));
+  if (n_corner) *n_corner = ncs[0];
+  if (n_surf) *n_surf = ncs[1];
+  const int pass = g.iter - 1;  // the job's last pass ran before its last solve
+  if (desc) {
+    *desc = fbr_knn_desc{};
+    desc->iterations = g.iter;
+    if (pass >= 0 && pass < (int)c->knn_desc.size()) {
+      const KnnLaunchDesc& d = c->knn_desc[pass];
+      desc->r = d.R; desc->rx = d.RX; desc->flat = d.flat; desc->sparse = d.sparse;
+      desc->lpq = d.lpq; desc->fused = d.fused; desc->tiles = d.tiles;
+    }
+  }
+  const int64_t n = (int64_t)ncs[0] + ncs[1];
+  if (!cap) return FBR_OK;
+  if (cap < n) return FBR_ERR_CAPACITY;
+  float T[12];
+  if (pass >= 0) CK(fbr_memcpy_sync(T, c->knn_T_slot(), sizeof(T), hipMemcpyDeviceToHost));
+  else std::memcpy(T, g.T, sizeof(T));  // no pass ran (too few features): the guess's transform
+  std::vector<float4> pts((size_t)std::max<int64_t>(n, 1));
+  if (ncs[0]) CK(fbr_memcpy_sync(pts.data(), c->d_cornerDS, sizeof(float4) * ncs[0], hipMemcpyDeviceToHost));
+  if (ncs[1]) CK(fbr_memcpy_sync(pts.data() + ncs[0], c->d_surfDS, sizeof(float4) * ncs[1], hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n; ++i) {
+    const float4 p = pts[i];
+    queries[3 * i] = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
+    queries[3 * i + 1] = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
+    queries[3 * i + 2] = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+  }
+  for (int64_t i = 0; i < 5 * n; ++i) nbr[i] = -1;
+  const int ni = range[1] - range[0];
+  if (pass < 0 || ni <= 0) return FBR_OK;
+  if (range[0] < 0 || range[1] > c->max_items) return FBR_ERR_STATE;
+  std::vector<int4> items((size_t)ni);
+  std::vector<int32_t> raw((size_t)ni * 5 * 256);
+  CK(fbr_memcpy_sync(items.data(), c->d_items + range[0], sizeof(int4) * ni, hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(raw.data(), c->d_nbr + (int64_t)range[0] * 5 * 256, sizeof(int32_t) * raw.size(),
+                     hipMemcpyDeviceToHost));
+  for (int it = 0; it < ni; ++it) {
+    const int4 item = items[it];  // {job, 0 corner / 1 surf, first query, queries}
+    for (int slot = 0; slot < item.w && slot < 256; ++slot) {
+      const int64_t q = (item.y == 0 ? 0 : ncs[0]) + item.z + slot;
+      if (item.x != 0 || q < 0 || q >= n) return FBR_ERR_STATE;
+      const int32_t* o = raw.data() + (size_t)it * 5 * 256 + slot;
+      if (o[0] < 0) continue;
+      for (int k = 0; k < 5; ++k) nbr[5 * q + k] = o[k * 256];
+    }
+  }
   return FBR_OK;
 }
 

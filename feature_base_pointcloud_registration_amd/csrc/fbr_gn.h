@@ -785,6 +785,8 @@ __device__ void gn_solve_job(const GnArgs& a, int job, const double* acc, float*
   g.iter = iterCount + 1;
   const int sel = (int)acc[27];
   g.n_sel = sel;
+  if (a.knn_T)  // diagnostic read-back: the transform this iteration's kNN pass ran at
+    for (int k = 0; k < 12; ++k) a.knn_T[job * 12 + k] = g.T[k];
   if (a.trace) {
     // filled below after the update; pre-fill with the current pose for the early-return case
     for (int k = 0; k < 6; ++k) a.trace[((int64_t)job * a.max_iter + iterCount) * 6 + k] = g.pose[k];
@@ -864,6 +866,7 @@ void launch_gn_knn_rls(hipStream_t s, const GnArgs& a, int grid, int use_prev) {
   constexpr bool kOne = LPQ == 1;
   auto go = [&](auto rx) {
     constexpr int RX = decltype(rx)::value;
+    knn_launch_desc() = KnnLaunchDesc{R, RX, L ? 1 : 0, S ? 1 : 0, LPQ, F ? 1 : 0, 0};
     if constexpr (kOne)
       launch_one_item(s, a, grid, total, 0, k_gn_knn<R, RX, F, L, S, LPQ>, k_gn_loop_knn<R, RX, F, L, S, LPQ>, a,
                       use_prev);

@@ -409,7 +409,19 @@ struct GnArgs {
   const int32_t* nsurf;
   const int32_t* ferr;
   const int32_t* cropcnt;
+  // Single scans (diagnostic, fbr_diag_knn_last): k_gn_solve keeps the transform the iteration's
+  // kNN pass ran at, GnState::T before the step, here ([B][12]); null: not kept.  Last member: the
+  // kernels that do not read it keep their argument offsets.
+  float* knn_T;
 };
+// Which kernel the latest kNN launch of this thread ran (written by the host launchers of
+// fbr_gn.h / k_knn_tile.hip, read by the run driver for fbr_diag_knn_last): cells per side covering
+// 1 m along y / z (R) and x (RX), flat row queue, hashed-chunk grids, lanes per query, fused with
+// the residual, LDS block tiles.
+struct KnnLaunchDesc {
+  int32_t R, RX, flat, sparse, lpq, fused, tiles;
+};
+KnnLaunchDesc& knn_launch_desc();
 #ifdef FBR_KNN_STATS
 unsigned long long* knn_stats_buffer();
 #endif

@@ -111,6 +111,7 @@ GnArgs gn_args(fbr_ctx* c, const Sub& sb, bool trace) {
     a.ferr = c->d_err + j0;
     a.cropcnt = c->d_cropcnt + (int64_t)sb.in0 * 2;
   }
+  if (sb.stream_mode && sb.B == 1 && sb.j0 == 0) a.knn_T = c->knn_T_slot();  // fbr_diag_knn_last
   return a;
 }
 
@@ -362,6 +363,7 @@ void gn_run_start(fbr_ctx* c, GnRun& r, const Sub* subs, int nsub, bool trace) {
   r.nsub = nsub;
   r.gen = ++c->gn_gen;
   r.lag = knobs::gn_lag();
+  c->knn_last_valid = nsub == 1 && subs[0].stream_mode && subs[0].B == 1 && subs[0].j0 == 0;
   for (int k = 0; k < nsub; ++k) {
     r.subs[k] = subs[k];
     r.a[k] = gn_args(c, subs[k], trace);
@@ -501,6 +503,7 @@ int gn_run_pass(fbr_ctx* c, GnRun& r, bool block, bool* progress) {
         TIMED_ON(c, sb.st, "gn_loop", launch_gn_residual(sb.st, a1, grid));
       }
     }
+    if (c->knn_last_valid && it < (int)c->knn_desc.size()) c->knn_desc[it] = knn_launch_desc();  // fbr_diag_knn_last
     TIMED_ON(c, sb.st, "gn_solve", launch_gn_solve(sb.st, r.a[k], it, r.gen));
     r.it[k] = it + 1;
     *progress = true;

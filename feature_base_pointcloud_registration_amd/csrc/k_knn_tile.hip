@@ -417,6 +417,7 @@ bool launch_gn_knn_tile(hipStream_t s, const GnArgs& a, int grid, int iter) {
   const float rmax2 = 1.0f / (kFineInv * kFineInv);  // bounds up to one fine cell
   const int gq = std::max(1, std::min(grid, 16384));
   unsigned long long* st = knn_tile_stats_buffer();
+  knn_launch_desc() = KnnLaunchDesc{2, 8, 0, 0, 1, 0, 1};
   fbr_launch(k_bin_count, dim3(gq), dim3(kBinThreads), 0, s, a, iter, rmax2, st);
   fbr_launch(k_bin_scan, dim3(1), dim3(1024), 0, s, a, iter);
   fbr_launch(k_bin_scatter, dim3(gq), dim3(kBinThreads), 0, s, a);

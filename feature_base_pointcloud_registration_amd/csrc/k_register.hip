@@ -311,6 +311,11 @@ void launch_gn_knn_f(hipStream_t s, const GnArgs& a, int grid, int use_prev) {
   else launch_gn_knn_r<1, F>(s, a, grid, use_prev);                  // >= 1 m
 }
 
+KnnLaunchDesc& knn_launch_desc() {
+  static thread_local KnnLaunchDesc d{};
+  return d;
+}
+
 void launch_gn_knn(hipStream_t s, const GnArgs& a, int grid, int iter, bool fused) {
   const int use_prev = iter > 0;  // nbr holds this launch's previous iteration
   // no loop launch after this one (or the LDS-tile path, which covers every item itself)

@@ -818,6 +818,27 @@ int fbr_batch_labels(fbr_ctx* ctx, int job, int8_t* label, int64_t cap, int64_t*
  * launches keep float4; 0: the default; < 0: the switch is left as it is.  *point_bytes (may be
  * NULL) receives the record size of the latest batch launch's cloud: 12, 16, or 0 before any. */
 int fbr_diag_batch_cloud(fbr_ctx* ctx, int force_wide, int32_t* point_bytes);
+/* Diagnostic (tests): the last neighbour search of the latest single-scan registration on this
+ * context (fbr_register, fbr_register_trace, fbr_process_scan), i.e. the pass of its last
+ * LMOptimization call, which ran at the pose before that call's step.  *n_corner / *n_surf: the
+ * down-sampled query counts (stats n_corner_ds / n_surf_ds).  Per query, corner queries first, each
+ * in its cloud's order: queries[3 i ..] the map-frame position the pass searched from (float, its
+ * bits), nbr[5 i ..] the five map indices (positions in fbr_get_map's clouds) in (d2, index) order,
+ * or -1 five times when the search kept no correspondence.  *desc (may be NULL) names the kernel
+ * that ran the pass.  cap = 0 returns the counts and the descriptor only; FBR_ERR_CAPACITY when
+ * 0 < cap < *n_corner + *n_surf; FBR_ERR_STATE when the context's latest registration was not a
+ * single scan (none yet, or a batch launch since). */
+typedef struct fbr_knn_desc {
+  int32_t iterations; /* LMOptimization calls of the run; the pass read back is number iterations - 1 */
+  int32_t r, rx;      /* grid cells per side covering 1 m along y / z and along x */
+  int32_t flat;       /* 1: flat LDS row queue */
+  int32_t sparse;     /* 1: hashed-chunk grids */
+  int32_t lpq;        /* lanes per query (1 or 8) */
+  int32_t fused;      /* 1: fused with the residual (tail mode) */
+  int32_t tiles;      /* 1: LDS block tiles (with the grid search behind them) */
+} fbr_knn_desc;
+int fbr_diag_knn_last(fbr_ctx* ctx, int32_t* n_corner, int32_t* n_surf, float* queries /* [cap][3] */,
+                      int32_t* nbr /* [cap][5] */, int64_t cap, fbr_knn_desc* desc);
 /* Enqueue (on the ctx stream, after every launch in flight) a copy of the latest launch's per-job
  * pose records {pose[6] f32, iterations i32, status i32} = 32 B/job into `device_dst` (device
  * memory of the ctx's device, [n_jobs][8] x 4 B) — the payload of the cross-GPU pose all-gather. */
