@@ -16,8 +16,9 @@ import os
 import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
-                        FbrGmapResult, FbrLoopResult, FbrParams, FbrPgResult, FbrRegStats, FbrScMatch, PointCloud2,
-                        default_params, gmap_params, icp_params, loop_params, pg_params, ptr, sc_params)
+                        FbrGmapResult, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
+                        PointCloud2, default_params, gmap_params, icp_params, loop_params, pg_marginal_params, pg_params, ptr,
+                        sc_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
     "fbr_pg_params_default", "fbr_pg_reset", "fbr_pg_add_prior", "fbr_pg_add_between", "fbr_pg_add_between_poses",
     "fbr_pg_add_gps", "fbr_pg_add_loop", "fbr_pg_factor_count", "fbr_pg_optimize", "fbr_pg_poses", "fbr_pg_apply",
+    "fbr_pg_marginal_params_default", "fbr_pg_marginals", "fbr_pg_gps_gate",
     "fbr_gmap_params_default", "fbr_global_map_build", "fbr_global_map_get", "fbr_global_map_install",
     "fbr_global_map_save", "fbr_pcd_write_poses_ascii", "fbr_selftest_voxel_wide",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
@@ -151,6 +153,9 @@ def lib():
             "fbr_pg_optimize": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_pg_poses": (ctypes.c_int, [_VP, _VP, _I64, _VP]),
             "fbr_pg_apply": (ctypes.c_int, [_VP]),
+            "fbr_pg_marginal_params_default": (None, [_VP]),
+            "fbr_pg_marginals": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP]),
+            "fbr_pg_gps_gate": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP]),
             "fbr_gmap_params_default": (None, [_VP]),
             "fbr_global_map_build": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_global_map_get": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
@@ -732,6 +737,33 @@ class Context:
     def pg_apply(self):
         """correctPoses: the optimised poses, rounded to float, become the key poses."""
         _check(lib().fbr_pg_apply(self._h), "fbr_pg_apply")
+
+    def pg_marginals(self, nodes=None, raw=False, **params):
+        """Marginal covariances of key poses at the last optimise's poses: (cov float64 [n, 6, 6] in
+        tangent order [rotation; translation], fbr_pg_marginal_result as a dict; raw: the struct).
+        nodes: the node indices (None: every node in order); params: fbr_pg_marginal_params' fields
+        (rhs_chunk, max_work_bytes).  With status FBR_PG_NUMERICAL the covariances are zero."""
+        p = pg_marginal_params(**params)
+        r = FbrPgMarginalResult()
+        idx = None if nodes is None else np.ascontiguousarray(nodes, np.int64).reshape(-1)
+        if idx is None:  # the row count first, as pg_poses
+            rc = lib().fbr_pg_marginals(self._h, ctypes.byref(p), None, 0, None, 0, ctypes.byref(r))
+            if rc not in (0, -4) or (rc == -4 and r.n_out == 0):
+                _check(rc, "fbr_pg_marginals")
+            rows = r.n_out
+        else:
+            rows = len(idx)
+        cov = np.zeros((max(rows, 1), 6, 6), np.float64)
+        _check(lib().fbr_pg_marginals(self._h, ctypes.byref(p), None if idx is None else ptr(idx), rows, ptr(cov), len(cov),
+                                      ctypes.byref(r)), "fbr_pg_marginals")
+        return cov[:rows], (r if raw else r.as_dict())
+
+    def pg_gps_gate(self, threshold=25.0):
+        """addGPSFactor's covariance gate (mapOptmization.h:1561) on the last key pose: (wanted,
+        [cov_xx, cov_yy]); threshold = poseCovThreshold."""
+        wanted, xy = ctypes.c_int(0), np.zeros(2, np.float64)
+        _check(lib().fbr_pg_gps_gate(self._h, float(threshold), ctypes.byref(wanted), ptr(xy)), "fbr_pg_gps_gate")
+        return bool(wanted.value), xy
 
     # ---- global map (mapOptmization.h:485-521) ----
     def global_map_build(self, params=None, raw=False, **kw):

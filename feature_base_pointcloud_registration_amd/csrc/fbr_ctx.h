@@ -479,6 +479,12 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   Mapped<unsigned long long> h_pg_flag;     // host-mapped progress word, written by k_pg_decide
   unsigned long long* d_pg_flag = nullptr;  // not owning: h_pg_flag's device address
   unsigned long long pg_gen = 0;
+  // marginal covariances (fbr_pg_marginals): valid for the result above while the factor count is
+  // the one that optimise saw
+  int64_t pg_result_nf = -1;
+  GrowDev<double> d_pg_marg;       // every double array of a marginals call (fbr_pg.hip pg_marginals_run)
+  GrowDev<int32_t> d_pg_loops;     // the loop factors' indices, in factor order
+  GrowDev<int64_t> d_pg_nodes;     // the requested nodes, then the distinct ones in ascending order
 
   // ---- global map (fbr_gmap.hip) ----
   // The clouds of the last fbr_global_map_build, until the next build, fbr_keyframes_reset or

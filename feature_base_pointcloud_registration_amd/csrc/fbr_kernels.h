@@ -557,4 +557,30 @@ void launch_pg_pcg_init(hipStream_t s, const PgArgs& a, unsigned long long gen);
 void launch_pg_pcg_iter(hipStream_t s, const PgArgs& a, int it, int max_it, double tol2, unsigned long long gen);
 void launch_pg_retract(hipStream_t s, const PgArgs& a, const double* X, double* Xt);
 
+// ---- pose-graph marginal covariances (k_pg_marginals.hip; the arithmetic is fbr_pg.h's) ----
+struct PgMarg {
+  int64_t n, K, M;             // nodes, loop factors, M = 6 K: the order of C
+  int nlev;
+  PgLevel lev[kPgMaxLevels];   // launch_pg_factor's levels (lambda = 0); b, x: a chunk's columns [cols][6][n_l]
+  double* P[kPgMaxLevels];     // [36][n_l] the level's selected inverse: P[m] = S[m][m]
+  double* Q[kPgMaxLevels];     //           Q[m] = S[m][m-1]
+  const PgFactor* fac;
+  const double* lin;           // the linearised factors (PgArgs::lin)
+  const int32_t* loops;        // [K] the loop factors' indices
+  double* W;                   // [M][6][n] T0^-1 U^T; the requested nodes' lanes become Y
+  double* C;                   // [M][M] row-major: I + U W, then its Cholesky factor (lower)
+  PgState* st;                 // numerical: a bad pivot of C joins those of T0
+};
+constexpr int64_t kPgMargMaxChunk = 65535;  // columns of one launch_pg_marg_solve (a grid dimension)
+// P, Q of every level, walking up from the last
+void launch_pg_selinv(hipStream_t s, const PgMarg& a);
+// columns [c0, c0 + nc) of W, nc <= kPgMargMaxChunk, through the levels' b and x
+void launch_pg_marg_solve(hipStream_t s, const PgMarg& a, int64_t c0, int64_t nc);
+void launch_pg_marg_c(hipStream_t s, const PgMarg& a);
+void launch_pg_marg_chol(hipStream_t s, const PgMarg& a);
+// Y in place for the distinct nodes uniq [n_uniq] (null: every node), then Sigma_ii of nodes [n_out]
+// (null: every node) into out [n_out][36]
+void launch_pg_marg_cov(hipStream_t s, const PgMarg& a, const int64_t* uniq, int64_t n_uniq, const int64_t* nodes,
+                        int64_t n_out, double* out);
+
 }  // namespace fbr

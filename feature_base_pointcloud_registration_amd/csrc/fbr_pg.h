@@ -1,6 +1,7 @@
 // fbr_pg.h — the pose-graph arithmetic of include/fbr.h ("pose graph"), host and device, all in
 // double: Exp / Log / Jr^-1 of SO(3), the residual and Jacobians of a factor, the 6x6 Cholesky, one
-// level step of the block cyclic reduction with its index arithmetic, and the Euler conversion.
+// level step of the block cyclic reduction with its index arithmetic, the Euler conversion, and the
+// per-node steps of the marginal covariances (k_pg_marginals.hip; on the CPU fbr_pg_host.h).
 // k_posegraph.hip compiles these functions for the device and tests/native/pg_probe.cpp for the CPU,
 // so the tests check the kernels' arithmetic without a GPU.  The contract is the project's own
 // restatement of a pose-graph optimiser in GTSAM 4.0's default Pose3 chart; it is pinned by the
@@ -8,8 +9,9 @@
 //
 // Must be compiled with -ffp-contract=off, as everything here.
 //
-// Every loop below has constant bounds and is unrolled, so the small local arrays stay in registers
-// on the device (a runtime-indexed local array would go to scratch).
+// Every loop over a small local array has constant bounds and is unrolled, so the arrays stay in
+// registers on the device (a runtime-indexed local array would go to scratch); the loops that are
+// not unrolled (the marginals' row passes and dense steps) index memory only.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -603,6 +605,262 @@ PG_HD double pg_hp_node(int64_t n, int64_t m, const PgFactor* fac, const double*
 #pragma unroll
   for (int r = 0; r < 6; ++r) d = d + pm[r] * o[r];
   return d;
+}
+
+// ---- marginal covariances (include/fbr.h "marginal covariances") ----
+// Sigma = H^-1 with H = T0 + U^T U: T0 the undamped block-tridiagonal part, factored by the cyclic
+// reduction above with lambda = 0, U [6K x 6N] the K loop factors' whitened Jacobians.
+//   selected inversion of T0: per level and node P[m] = S[m][m], Q[m] = S[m][m-1] (S = that level's
+//     inverse), walking up from the last level (pg_selinv_top, pg_selinv_up); level 0's P is P_i.
+//   W = T0^-1 U^T: one cyclic-reduction solve per column (pg_cr_*_col; column c of a level's b and
+//     x is the [6][n] vector at offset c * 6 * n, so W is [6K][6][N] and W_i^T is a strided view)
+//   C = I + U W (pg_marg_c_entry), C = Lc Lc^T (pg_dense_chol_block, pg_dense_panel_row,
+//     pg_dense_trail_entry), Y_i = Lc^-1 W_i^T in place (pg_marg_forward), and
+//   Sigma_ii = P_i - Y_i^T Y_i (pg_marg_final).
+
+// Row r of (L L^T)^-1 (= its column r)
+PG_HD void pg_chol6_inv_row(const double* L, int r, double* x) {
+#pragma unroll
+  for (int e = 0; e < 6; ++e) x[e] = e == r ? 1.0 : 0.0;
+  pg_chol6_solve(L, x);
+}
+
+// The last level's single node: P[0] = D^-1.
+PG_HD void pg_selinv_top(const PgLevel& lv, double* P) {
+  double L[36], x[6];
+  pg_ld36(lv.L, lv.n, 0, L);
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    pg_chol6_inv_row(L, r, x);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) P[(6 * r + c) * lv.n] = x[c];
+  }
+}
+
+// Node m of a level from the next level's nP, nQ (nn nodes).  Even m = 2q: P[m] = nP[q].  Odd k,
+// a = (k - 1) / 2, Sl = nP[a], Sr = nP[a+1], Srl = nQ[a+1]:
+//   Kl = S[k][k-1] = -G_k Sl - H_k Srl        Kr = S[k][k+1] = -G_k Srl^T - H_k Sr
+//   P[k] = D_k^-1 - Kl G_k^T - Kr H_k^T       Q[k] = Kl        Q[k+1] = Kr^T
+// (terms of an absent right neighbour dropped).  The odd node writes Q[k+1]: no two nodes write one
+// block.  Q[0] is never written or read.
+PG_HD void pg_selinv_up(const PgLevel& lv, const double* nP, const double* nQ, int64_t nn, double* P, double* Q,
+                        int64_t m) {
+  const int64_t n = lv.n;
+  if (!(m & 1)) {
+    double S[36];
+    pg_ld36(nP, nn, m >> 1, S);
+    pg_st36(P, n, m, S);
+    return;
+  }
+  const int64_t a = (m - 1) >> 1;
+  const bool right = m + 1 < n;
+  // Two passes over the rows, neither unrolled, the first leaving Kl and Kr in Q: a thread holds
+  // three 6x6 blocks at a time and not six (registers on the device).
+  {
+    double Sl[36], Srl[36], Sr[36];
+    pg_ld36(nP, nn, a, Sl);
+    if (right) {
+      pg_ld36(nP, nn, a + 1, Sr);
+      pg_ld36(nQ, nn, a + 1, Srl);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 36; ++e) Sr[e] = Srl[e] = 0.0;
+    }
+#pragma unroll 1
+    for (int r = 0; r < 6; ++r) {
+      double g[6], h[6];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) {
+        g[k] = lv.G[(6 * r + k) * n + m];
+        h[k] = right ? lv.H[(6 * r + k) * n + m] : 0.0;
+      }
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0, t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = s + g[k] * Sl[6 * k + c];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s = s + h[k] * Srl[6 * k + c];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t = t + g[k] * Srl[6 * c + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) t = t + h[k] * Sr[6 * k + c];
+        Q[(6 * r + c) * n + m] = -s;
+        if (right) Q[(6 * c + r) * n + m + 1] = -t;
+      }
+    }
+  }
+  double G[36], H[36], L[36];
+  pg_ld36(lv.G, n, m, G);
+  pg_ld36(lv.L, n, m, L);
+  if (right) {
+    pg_ld36(lv.H, n, m, H);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 36; ++e) H[e] = 0.0;
+  }
+#pragma unroll 1
+  for (int r = 0; r < 6; ++r) {
+    double kl[6], kr[6], di[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      kl[c] = Q[(6 * r + c) * n + m];
+      kr[c] = right ? Q[(6 * c + r) * n + m + 1] : 0.0;
+    }
+    pg_chol6_inv_row(L, r, di);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + kl[k] * G[6 * c + k];
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s = s + kr[k] * H[6 * c + k];
+      P[(6 * r + c) * n + m] = di[c] - s;
+    }
+  }
+}
+
+// The cyclic-reduction solve of right-hand-side column c: the steps above on the [6][n] vectors at
+// offset c * 6 * n of each level's b and x.
+PG_HD PgLevel pg_level_col(const PgLevel& lv, int64_t c) {
+  PgLevel o = lv;
+  o.b = lv.b + c * 6 * lv.n;
+  o.x = lv.x + c * 6 * lv.n;
+  return o;
+}
+PG_HD void pg_cr_reduce_col(const PgLevel& lv, const PgLevel& nx, int64_t q, int64_t c) {
+  pg_cr_reduce(pg_level_col(lv, c), pg_level_col(nx, c), q);
+}
+PG_HD void pg_cr_top_col(const PgLevel& lv, int64_t c) { pg_cr_top(pg_level_col(lv, c)); }
+PG_HD void pg_cr_backsub_col(const PgLevel& lv, const PgLevel& nx, int64_t m, int64_t c) {
+  pg_cr_backsub(pg_level_col(lv, c), pg_level_col(nx, c), m);
+}
+
+// Entry e of node `side` (0: i, 1: j) of column col = 6 f + r of U^T, f the loop factor fk's rank
+// among the loop factors: row r of its whitened J_side.
+PG_HD double pg_marg_rhs_entry(const double* lin, int32_t fk, int r, int side, int e) {
+  return lin[(int64_t)fk * kPgLin + 6 + 36 * side + 6 * r + e];
+}
+
+// C[row][col] = delta + U[row] . W[:, col], row = 6 f + r: J_i's row r against node i's six entries
+// of column col, then J_j's against node j's.
+PG_HD double pg_marg_c_entry(const PgFactor* fac, const double* lin, const int32_t* loops, const double* W, int64_t n,
+                             int64_t row, int64_t col) {
+  const int32_t fk = loops[row / 6];
+  const int r = (int)(row % 6);
+  const double* Ji = lin + (int64_t)fk * kPgLin + 6 + 6 * r;
+  const double* Jj = Ji + 36;
+  const double* w = W + col * 6 * n;
+  const int64_t i = fac[fk].i, j = fac[fk].j;
+  double s = row == col ? 1.0 : 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) s = s + Ji[e] * w[e * n + i];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) s = s + Jj[e] * w[e * n + j];
+  return s;
+}
+
+// ---- dense Cholesky of C [M][M] row-major, lower triangle, in place, blocked right-looking ----
+constexpr int kPgPanel = 32;  // columns of a panel
+
+// The panel's diagonal block Ld (nb x nb, leading dimension ld), right-looking: false on a bad pivot
+// (taken as 1, as pg_chol6).  An entry's updates come in column order whichever way they are
+// scheduled, so a parallel version gives the same bits.
+PG_HD bool pg_dense_chol_block(double* Ld, int64_t ld, int nb) {
+  bool ok = true;
+  for (int j = 0; j < nb; ++j) {
+    double d = Ld[j * ld + j];
+    if (!(d > 0.0) || !(d < INFINITY)) {
+      ok = false;
+      d = 1.0;
+    }
+    const double l = sqrt(d);
+    Ld[j * ld + j] = l;
+    for (int i = j + 1; i < nb; ++i) Ld[i * ld + j] = Ld[i * ld + j] / l;
+    for (int i = j + 1; i < nb; ++i)
+      for (int k = j + 1; k <= i; ++k) Ld[i * ld + k] = Ld[i * ld + k] - Ld[i * ld + j] * Ld[k * ld + j];
+  }
+  return ok;
+}
+// Row i > the panel [j0, j0 + nb) of A: A[i][j0 ..] = A[i][j0 ..] Ld^-T, in place.
+PG_HD void pg_dense_panel_row(double* A, int64_t M, int64_t j0, int nb, const double* Ld, int64_t ld, int64_t i) {
+  double* a = A + i * M + j0;
+  for (int k = 0; k < nb; ++k) {
+    double s = a[k];
+    for (int t = 0; t < k; ++t) s = s - a[t] * Ld[k * ld + t];
+    a[k] = s / Ld[k * ld + k];
+  }
+}
+// Trailing entry (i, j), j <= i, both past the panel: A[i][j] -= sum_k A[i][j0 + k] A[j][j0 + k].
+PG_HD void pg_dense_trail_entry(double* A, int64_t M, int64_t j0, int nb, int64_t i, int64_t j) {
+  double s = 0.0;
+  for (int k = 0; k < nb; ++k) s = s + A[i * M + j0 + k] * A[j * M + j0 + k];
+  A[i * M + j] = A[i * M + j] - s;
+}
+
+// Y = Lc^-1 W_i^T for entry e of node i, in place on W's lane (e, i): y[c] = W[(6 c + e) n + i].
+// Eight rows at a time, so that y[k] is read once per eight rows; each row's sum in column order.
+PG_HD void pg_marg_forward(const double* Lc, int64_t M, double* W, int64_t n, int64_t i, int e) {
+  double* y = W + (int64_t)e * n + i;
+  const int64_t st = 6 * n;
+  for (int64_t r0 = 0; r0 < M; r0 += 8) {
+    double acc[8];
+    const double* Lr[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int64_t row = r0 + u < M ? r0 + u : M - 1;  // rows past the end repeat the last one and are not stored
+      Lr[u] = Lc + row * M;
+      acc[u] = y[row * st];
+    }
+    for (int64_t k = 0; k < r0; ++k) {
+      const double yk = y[k * st];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc[u] = acc[u] - Lr[u][k] * yk;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (r0 + u < M) {  // (so r0 + t < M too)
+        double s = acc[u];
+#pragma unroll
+        for (int t = 0; t < u; ++t) s = s - Lr[u][r0 + t] * acc[t];
+        acc[u] = s / Lr[u][r0 + u];
+        y[(r0 + u) * st] = acc[u];
+      }
+    }
+  }
+}
+
+// addGPSFactor's gate (mapOptmization.h:1561) on a node's marginal [36]: a GPS factor is wanted
+// unless both poseCovariance(3,3) and (4,4) are below the threshold.
+PG_HD int pg_gps_gate_wanted(const double* cov, double threshold) {
+  return !(cov[6 * 3 + 3] < threshold && cov[6 * 4 + 4] < threshold) ? 1 : 0;
+}
+
+// Sigma_ii = P_i - Y_i^T Y_i into out [36] row-major: r <= c computed (the sum over Y's rows in
+// order) and mirrored.
+PG_HD void pg_marg_final(const double* P, const double* Y, int64_t M, int64_t n, int64_t i, double* out) {
+  double s[21];
+#pragma unroll
+  for (int k = 0; k < 21; ++k) s[k] = 0.0;
+  for (int64_t col = 0; col < M; ++col) {
+    double y[6];
+    pg_ld6(Y + col * 6 * n, n, i, y);
+#pragma unroll
+    for (int r = 0; r < 6; ++r)
+#pragma unroll
+      for (int c = r; c < 6; ++c) {
+        const int k = 6 * r - r * (r - 1) / 2 + (c - r);  // (r, c)'s place among the 21 pairs
+        s[k] = s[k] + y[r] * y[c];
+      }
+  }
+#pragma unroll
+  for (int r = 0; r < 6; ++r)
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      const double v = P[(6 * r + c) * n + i] - s[6 * r - r * (r - 1) / 2 + (c - r)];
+      out[6 * r + c] = v;
+      out[6 * c + r] = v;
+    }
 }
 
 }  // namespace fbr

@@ -257,6 +257,120 @@ int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
     }
   }
   c->pg_result_n = n;
+  c->pg_result_nf = (int64_t)c->pg_factors.size();
+  return FBR_OK;
+}
+
+constexpr int kPgMargChunk = 48;                             // fbr_pg_marginal_params.rhs_chunk's default
+constexpr int64_t kPgMargMaxWork = (int64_t)2 << 30;         // ... and max_work_bytes' (2 GiB)
+
+// Sigma_ii of the requested nodes at the last optimise's poses (include/fbr.h "marginal
+// covariances").  Everything is enqueued without waiting; the host reads the result and the status
+// word once, at the end.
+int pg_marginals_run(fbr_ctx* c, const fbr_pg_marginal_params& P, const int64_t* nodes, int64_t n_nodes, double* cov_out,
+                     int64_t cap, fbr_pg_marginal_result* out) {
+  const int64_t n = (int64_t)c->kf_poses.size();
+  if (c->pg_result_n < 0 || c->pg_result_n != n || c->pg_result_nf != (int64_t)c->pg_factors.size()) return FBR_ERR_STATE;
+  const int64_t n_out = nodes ? n_nodes : n;
+  for (int64_t o = 0; nodes && o < n_out; ++o)
+    if (nodes[o] < 0 || nodes[o] >= n) return FBR_ERR_INVALID_ARG;
+  std::vector<int32_t> loops;
+  for (size_t k = 0; k < c->pg_factors.size(); ++k)
+    if (c->pg_factors[k].loop) loops.push_back((int32_t)k);
+  const int64_t K = (int64_t)loops.size(), M = 6 * K;
+  out->n_nodes = (int32_t)n;
+  out->n_loop_factors = (int32_t)K;
+  out->n_out = (int32_t)n_out;
+  if (n_out > cap) return FBR_ERR_CAPACITY;
+  if (n_out == 0) {
+    out->status = FBR_PG_EMPTY;
+    return FBR_OK;
+  }
+  int64_t tot = 0;
+  (void)pg_cr_levels(n, &tot);
+  const int64_t chunk = std::min(std::min<int64_t>(P.rhs_chunk > 0 ? P.rhs_chunk : kPgMargChunk, std::max<int64_t>(M, 1)),
+                                 kPgMargMaxChunk);
+  const int64_t max_work = P.max_work_bytes > 0 ? P.max_work_bytes : kPgMargMaxWork;
+  // P and Q of every level, W, the chunk's b of every level and x of the levels after the first, C,
+  // the output staging buffer (in double first: the products overflow an int64 long after the bound)
+  const double words_d = 72.0 * (double)tot + 6.0 * (double)std::max<int64_t>(M, 1) * (double)n +
+                         6.0 * (double)chunk * (double)(2 * tot - n) + (double)M * (double)M + 36.0 * (double)n_out;
+  if (8.0 * words_d > (double)max_work) {
+    out->work_bytes = words_d < 1e18 ? (int64_t)(8.0 * words_d) : INT64_MAX;
+    return FBR_ERR_CAPACITY;
+  }
+  const int64_t words = 72 * tot + 6 * std::max<int64_t>(M, 1) * n + 6 * chunk * (2 * tot - n) + M * M + 36 * n_out;
+  out->work_bytes = 8 * words;
+  PgPlan pl;
+  int rc = pg_prepare(c, n, &pl);
+  if (rc) return rc;
+  const PgArgs& a = pl.a;
+  // the distinct requested nodes in ascending order: Y is computed in place, once per node
+  std::vector<int64_t> idx;
+  int64_t n_uniq = n_out;
+  if (nodes) {
+    idx.assign(nodes, nodes + n_out);
+    std::vector<int64_t> u(idx);
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+    n_uniq = (int64_t)u.size();
+    idx.insert(idx.end(), u.begin(), u.end());
+  }
+  rc = grow(c->d_pg_marg, words, 0, c->stream);
+  if (!rc) rc = grow(c->d_pg_loops, std::max<int64_t>(K, 1), 0, c->stream);
+  if (!rc) rc = grow(c->d_pg_nodes, std::max<int64_t>((int64_t)idx.size(), 1), 0, c->stream);
+  if (rc) return rc;
+  std::vector<double> X0((size_t)(12 * n));
+  for (int64_t i = 0; i < n; ++i) pg_pose_from_euler(&c->pg_result[6 * i], &X0[12 * i]);
+  CK(hipMemcpyAsync(pl.X, X0.data(), sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->stream));
+  if (K) CK(hipMemcpyAsync(c->d_pg_loops, loops.data(), sizeof(int32_t) * K, hipMemcpyHostToDevice, c->stream));
+  if (nodes) CK(hipMemcpyAsync(c->d_pg_nodes, idx.data(), sizeof(int64_t) * idx.size(), hipMemcpyHostToDevice, c->stream));
+  CK(fbr_sync(c->stream));  // the pageable copies
+  PgMarg m{};
+  m.n = n;
+  m.K = K;
+  m.M = M;
+  m.nlev = a.nlev;
+  m.fac = a.fac;
+  m.lin = a.lin;
+  m.loops = c->d_pg_loops;
+  m.st = a.st;
+  double* w = c->d_pg_marg;
+  auto take = [&w](int64_t count) {
+    double* p = w;
+    w += count;
+    return p;
+  };
+  for (int l = 0; l < a.nlev; ++l) {
+    m.lev[l] = a.lev[l];
+    m.P[l] = take(36 * a.lev[l].n);
+    m.Q[l] = take(36 * a.lev[l].n);
+    m.lev[l].b = take(6 * chunk * a.lev[l].n);
+    m.lev[l].x = l ? take(6 * chunk * a.lev[l].n) : nullptr;  // level 0's x is the chunk's part of W
+  }
+  m.W = take(6 * std::max<int64_t>(M, 1) * n);
+  m.C = take(M * M);
+  double* d_out = take(36 * n_out);
+  const int64_t* d_nodes = nodes ? (const int64_t*)c->d_pg_nodes : nullptr;
+  TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, pl.X, 1, 0));
+  TIMED(c, "pg_assemble", launch_pg_assemble(c->stream, a));
+  TIMED(c, "pg_factor", launch_pg_factor(c->stream, a, 0.0));  // lambda = 0: D = D0 + 0 * hd, the undamped T0
+  TIMED(c, "pg_selinv", launch_pg_selinv(c->stream, m));
+  for (int64_t c0 = 0; c0 < M; c0 += chunk)
+    TIMED(c, "pg_marg_solve", launch_pg_marg_solve(c->stream, m, c0, std::min(chunk, M - c0)));
+  TIMED(c, "pg_marg_c", launch_pg_marg_c(c->stream, m));
+  TIMED(c, "pg_marg_chol", launch_pg_marg_chol(c->stream, m));
+  TIMED(c, "pg_marg_cov", launch_pg_marg_cov(c->stream, m, d_nodes ? d_nodes + n_out : nullptr, n_uniq, d_nodes, n_out, d_out));
+  CK(hipGetLastError());
+  PgState st;
+  CK(hipMemcpyAsync(cov_out, d_out, sizeof(double) * 36 * n_out, hipMemcpyDeviceToHost, c->stream));
+  CK(hipMemcpyAsync(&st, c->d_pg_state, sizeof(PgState), hipMemcpyDeviceToHost, c->stream));
+  CK(fbr_sync(c->stream));
+  out->status = FBR_PG_CONVERGED;
+  if (st.numerical) {
+    out->status = FBR_PG_NUMERICAL;
+    std::memset(cov_out, 0, sizeof(double) * 36 * n_out);
+  }
   return FBR_OK;
 }
 
@@ -375,6 +489,40 @@ int fbr_pg_poses(fbr_ctx* c, double* poses_out, int64_t cap, int64_t* n) {
   *n = c->pg_result_n;
   if (cap < c->pg_result_n) return FBR_ERR_CAPACITY;
   std::memcpy(poses_out, c->pg_result.data(), sizeof(double) * 6 * c->pg_result_n);
+  return FBR_OK;
+}
+
+void fbr_pg_marginal_params_default(fbr_pg_marginal_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));  // rhs_chunk = 0 and max_work_bytes = 0: the defaults (48 columns, 2 GiB)
+}
+
+int fbr_pg_marginals(fbr_ctx* c, const fbr_pg_marginal_params* p, const int64_t* nodes, int64_t n_nodes, double* cov_out,
+                     int64_t cap, fbr_pg_marginal_result* out) {
+  if (!c || !p || !out || cap < 0 || (cap && !cov_out) || (nodes && n_nodes < 0) || p->rhs_chunk < 0 ||
+      p->max_work_bytes < 0)
+    return FBR_ERR_INVALID_ARG;
+  CK(enter(c));
+  std::memset(out, 0, sizeof(*out));
+  return pg_marginals_run(c, *p, nodes, n_nodes, cov_out, cap, out);
+}
+
+int fbr_pg_gps_gate(fbr_ctx* c, double pose_cov_threshold, int* wanted, double cov_xy[2]) {
+  if (!c || !wanted || !(pose_cov_threshold == pose_cov_threshold)) return FBR_ERR_INVALID_ARG;
+  fbr_pg_marginal_params p;
+  fbr_pg_marginal_params_default(&p);
+  fbr_pg_marginal_result r;
+  const int64_t last = (int64_t)c->kf_poses.size() - 1;
+  if (last < 0) return FBR_ERR_STATE;
+  double cov[36];
+  const int rc = fbr_pg_marginals(c, &p, &last, 1, cov, 1, &r);
+  if (rc) return rc;
+  const bool known = r.status == FBR_PG_CONVERGED;  // no covariance: unbounded, and the factor is wanted
+  *wanted = known ? pg_gps_gate_wanted(cov, pose_cov_threshold) : 1;
+  if (cov_xy) {
+    cov_xy[0] = known ? cov[6 * 3 + 3] : INFINITY;
+    cov_xy[1] = known ? cov[6 * 4 + 4] : INFINITY;
+  }
   return FBR_OK;
 }
 

@@ -164,6 +164,23 @@ def pg_params(**kw):
     return p
 
 
+class FbrPgMarginalParams(_Dictable):
+    _fields_ = [("rhs_chunk", ctypes.c_int32), ("reserved_", ctypes.c_int32 * 3), ("max_work_bytes", ctypes.c_int64)]
+
+
+class FbrPgMarginalResult(_Dictable):
+    _fields_ = [("status", ctypes.c_int32), ("n_nodes", ctypes.c_int32), ("n_loop_factors", ctypes.c_int32),
+                ("n_out", ctypes.c_int32), ("work_bytes", ctypes.c_int64)]
+
+
+def pg_marginal_params(**kw):
+    """fbr_pg_marginal_params_default: rhs_chunk 0 (48 columns per pass), max_work_bytes 0 (2 GiB)."""
+    p = FbrPgMarginalParams()
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 # global map (include/fbr.h "global map")
 FBR_GMAP_SAVE_GLOBAL = 1
 

@@ -521,8 +521,9 @@ int fbr_perform_loop_closure_sc(fbr_ctx* ctx, double stamp, const fbr_loop_param
  * (:743-758) and correctPoses (:1735-1770), as a batch optimiser over the keyframe store, so that
  * "loop closed" can end in corrected key poses without GTSAM.  This is the project's own
  * restatement: it is pinned by a NumPy model in tests/ and not against GTSAM or iSAM2.  What stays
- * with the caller: iSAM2's incremental updates, marginal covariances (poseCovariance, and with it
- * addGPSFactor's covariance gate), robust kernels and IMU preintegration factors.
+ * with the caller: iSAM2's incremental updates, robust kernels and IMU preintegration factors.
+ * The marginal covariances of the key poses (poseCovariance, :1706) and addGPSFactor's covariance
+ * gate (:1561) are below ("marginal covariances").
  *
  * Nodes 0 .. N-1 are the keyframes in the store when fbr_pg_optimize is called; node i starts from
  * the stored key pose i.  A pose is (R, t), R = Rz(yaw) Ry(pitch) Rx(roll) as fbr_affine_from_pose;
@@ -635,6 +636,63 @@ int fbr_pg_poses(fbr_ctx* ctx, double* poses_out /* [n][6] */, int64_t cap, int6
  * float through fbr_keyframes_set_pose (index and time kept).  FBR_ERR_STATE when there is no result
  * or the store has changed size since the optimise. */
 int fbr_pg_apply(fbr_ctx* ctx);
+
+/* ---- pose graph: marginal covariances of the key poses and the GPS gate -------------
+ * The reference reads poseCovariance = isam->marginalCovariance(last) after every update (:1706) and
+ * adds a GPS factor only while poseCovariance(3,3) or (4,4) is at least poseCovThreshold (:1561).
+ *
+ * Definition: Sigma = H^-1, H = J^T J the UNDAMPED normal matrix (lambda = 0) of every factor in the
+ * list, linearised at the last optimise's poses exactly as fbr_pg_poses returns them (the double
+ * Euler angles, converted back by R = Rz(yaw) Ry(pitch) Rx(roll)), so that a model reproduces the
+ * point from public outputs.  The marginal of node i is the 6x6 diagonal block Sigma_ii, row-major,
+ * in the chart's tangent order [rotation; translation]; the translation part is in the body frame
+ * of T_i, as GTSAM's Pose3 marginal is; entries (3,3) and (4,4) are what the reference reads.  The
+ * output is exactly symmetric: r <= c is computed and mirrored.
+ *
+ * Method: H = T0 + U^T U, T0 the undamped block-tridiagonal part and U [6K x 6N] the K loop factors'
+ * whitened Jacobians (two 6x6 blocks per block row).  Sigma_ii = P_i - Y_i^T Y_i with
+ *   P_i = (T0^-1)_ii,  W = T0^-1 U^T,  C = I + U W = Lc Lc^T,  Y = Lc^-1 W^T.
+ * P_i by selected inversion through the levels of the optimiser's block cyclic reduction of T0:
+ * walking up from the last level with P[m] = S[m][m] and Q[m] = S[m][m-1] per node (S the level's
+ * inverse).  Last level: P[0] = D^-1.  Even node m = 2q: P[m] = next.P[q].  Odd node k, a = (k-1)/2,
+ * Sl = next.P[a], Sr = next.P[a+1], Srl = next.Q[a+1], G_k = D_k^-1 T[k][k-1], H_k = D_k^-1 T[k][k+1]:
+ *   S[k][k-1] = -G_k Sl - H_k Srl          S[k][k+1] = -G_k Srl^T - H_k Sr
+ *   P[k] = D_k^-1 - S[k][k-1] G_k^T - S[k][k+1] H_k^T     Q[k] = S[k][k-1]     Q[k+1] = S[k][k+1]^T
+ * (terms of an absent right neighbour dropped).  W by one cyclic-reduction solve per column, rhs_chunk
+ * columns per pass; C by a dense blocked Cholesky (panels of 32 columns).
+ *
+ * T0 must be positive definite: an unbroken chain of consecutive between factors and at least one
+ * prior or gps factor.  A non-positive or non-finite pivot of T0 or of C: status FBR_PG_NUMERICAL and
+ * a zeroed output (return value FBR_OK).  Under the reference's prior (variance 1e8 on the
+ * translation) cond(H) ~ 1e16 and the covariances carry two to three digits: enough for the gate,
+ * whose two sides are orders of magnitude apart.
+ *
+ * FBR_ERR_STATE without an optimise result, or when the store's size or the factor count has changed
+ * since that optimise.  FBR_ERR_INVALID_ARG for a node index out of range.  FBR_ERR_CAPACITY (with
+ * out->n_out set) when cap < the rows asked for, and (with out->work_bytes set) when the device
+ * work space, W (6N x 6K doubles) plus P, Q, the chunk's right-hand sides, C and the output, exceeds
+ * max_work_bytes.  Two calls return the same bytes, whatever rhs_chunk and whichever nodes are asked
+ * for: no float or double atomics, every sum in a fixed order.  One device-to-host copy of the result
+ * and one read of the status word per call; nothing waits in between. */
+typedef struct fbr_pg_marginal_params {
+  int32_t rhs_chunk;       /* columns of U^T solved per pass; 0 = default (48) */
+  int32_t reserved_[3];
+  int64_t max_work_bytes;  /* 0 = default (2 GiB) */
+} fbr_pg_marginal_params;
+typedef struct fbr_pg_marginal_result {
+  int32_t status;          /* FBR_PG_CONVERGED (ok) | FBR_PG_NUMERICAL | FBR_PG_EMPTY (no row asked for) */
+  int32_t n_nodes, n_loop_factors, n_out;
+  int64_t work_bytes;
+} fbr_pg_marginal_result;
+void fbr_pg_marginal_params_default(fbr_pg_marginal_params* p);
+/* nodes == NULL: every node in order (n_nodes ignored, cap = rows of cov_out).  A node may be named
+ * more than once. */
+int fbr_pg_marginals(fbr_ctx* ctx, const fbr_pg_marginal_params* p, const int64_t* nodes, int64_t n_nodes,
+                     double* cov_out /* [n][36] */, int64_t cap, fbr_pg_marginal_result* out);
+/* addGPSFactor's gate (:1561) on the last node: *wanted = !(cov33 < thr && cov44 < thr); cov_xy
+ * (optional) = {cov33, cov44}.  Without a covariance (FBR_PG_NUMERICAL) the factor is wanted and
+ * cov_xy is infinite.  Errors as fbr_pg_marginals. */
+int fbr_pg_gps_gate(fbr_ctx* ctx, double pose_cov_threshold, int* wanted, double cov_xy[2]);
 
 /* ---- global map (visualizeGlobalMapThread's save block, mapOptmization.h:485-521) -------------
  * Turns the keyframe store into the map the localiser loads: every keyframe's corner / surf cloud

@@ -400,6 +400,26 @@ class MapOptimization {
     return r;
   }
   void correctPoses() { check(fbr_pg_apply(c_.get()), "fbr_pg_apply"); }
+  /* poseCovariance (:1706) of the key poses `nodes` (empty: every node, n of them) at the last
+   * optimise's poses: cov [rows][36] row-major, tangent order [rotation; translation]. */
+  fbr_pg_marginal_result pgMarginals(std::vector<double>* cov, const std::vector<int64_t>& nodes = {}, int64_t n = 0,
+                                     const fbr_pg_marginal_params* mp = nullptr) {
+    fbr_pg_marginal_params p;
+    fbr_pg_marginal_params_default(&p);
+    if (mp) p = *mp;
+    fbr_pg_marginal_result r{};
+    const int64_t rows = nodes.empty() ? n : (int64_t)nodes.size();
+    cov->assign((size_t)rows * 36, 0.0);
+    check(fbr_pg_marginals(c_.get(), &p, nodes.empty() ? nullptr : nodes.data(), rows, cov->data(), rows, &r),
+          "fbr_pg_marginals");
+    return r;
+  }
+  /* addGPSFactor's covariance gate (:1561) on the last key pose. */
+  bool pgGpsGate(double poseCovThreshold, double cov_xy[2] = nullptr) {
+    int wanted = 0;
+    check(fbr_pg_gps_gate(c_.get(), poseCovThreshold, &wanted, cov_xy), "fbr_pg_gps_gate");
+    return wanted != 0;
+  }
 
   /* visualizeGlobalMapThread's save block (:485-521) in three steps: build the global map from the
    * keyframe store (params null: the reference's mode; wide = 1 is this project's extension for maps
