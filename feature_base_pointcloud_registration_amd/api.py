@@ -17,8 +17,8 @@ import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
                         FbrGmapResult, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
-                        PointCloud2, default_params, gmap_params, icp_params, loop_params, pg_marginal_params, pg_params, ptr,
-                        sc_params)
+                        POSE_SCORE, PointCloud2, default_params, gmap_params, icp_params, loop_params,
+                        pg_marginal_params, pg_params, pose_lattice, ptr, sc_params, score_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "fbr_pg_marginal_params_default", "fbr_pg_marginals", "fbr_pg_gps_gate",
     "fbr_gmap_params_default", "fbr_global_map_build", "fbr_global_map_get", "fbr_global_map_install",
     "fbr_global_map_save", "fbr_pcd_write_poses_ascii", "fbr_selftest_voxel_wide",
+    "fbr_score_params_default", "fbr_score_poses", "fbr_pose_search",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -163,6 +164,9 @@ def lib():
             "fbr_global_map_save": (ctypes.c_int, [_VP, ctypes.c_char_p, _I32]),
             "fbr_pcd_write_poses_ascii": (ctypes.c_int, [ctypes.c_char_p, _VP, _I64]),
             "fbr_selftest_voxel_wide": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_float, _VP, _VP]),
+            "fbr_score_params_default": (None, [_VP]),
+            "fbr_score_poses": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP]),
+            "fbr_pose_search": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
             "fbr_comm_create_local": (ctypes.c_int, [_VP, _VP, ctypes.c_int, ctypes.c_int]),
@@ -819,6 +823,70 @@ class Context:
             if st["status"] == 0 and st["converged"] and not st["degenerate"] and (
                     winner < 0 or st["n_sel"] > hyps[winner][2]["n_sel"]):
                 winner = len(hyps) - 1
+        return hyps, winner
+
+    # ---- pose scoring (include/fbr.h "pose scoring") ----
+    def score_poses(self, corner, surf, poses, score=None, keys=False):
+        """How well a scan-frame cloud (corner, surf: the mapping-leaf down-samples) fits the installed
+        map at each pose [roll, pitch, yaw, x, y, z]: a POSE_SCORE record array [n_poses]; with keys,
+        also the correspondence keys uint64 [n_poses, n_corner + n_surf] (~0: no inlier)."""
+        sp = score if score is not None else score_params()
+        corner = _as_points(corner, POINT_XYZI)
+        surf = _as_points(surf, POINT_XYZI)
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        out = np.zeros(max(len(poses), 1), POSE_SCORE)
+        nn = np.zeros((max(len(poses), 1), max(len(corner) + len(surf), 1)), np.uint64) if keys else None
+        _check(lib().fbr_score_poses(self._h, ctypes.byref(sp), ptr(corner) if len(corner) else None, len(corner),
+                                     ptr(surf) if len(surf) else None, len(surf), ptr(poses) if len(poses) else None,
+                                     len(poses), ptr(out), None if nn is None else ptr(nn)), "fbr_score_poses")
+        out = out[:len(poses)]
+        return (out, nn[:len(poses), :len(corner) + len(surf)]) if keys else out
+
+    def pose_search(self, corner, surf, seeds, lattice, top_k=3, score=None):
+        """Score the lattice of hypotheses around the seed poses [n_seeds, 6] and return the top_k best
+        by (fitness, hypothesis index): (poses float32 [m, 6], POSE_SCORE [m], hypothesis indices int64 [m])."""
+        sp = score if score is not None else score_params()
+        corner = _as_points(corner, POINT_XYZI)
+        surf = _as_points(surf, POINT_XYZI)
+        seeds = np.ascontiguousarray(seeds, np.float32).reshape(-1, 6)
+        k = max(int(top_k), 0)
+        poses = np.zeros((max(k, 1), 6), np.float32)
+        sc = np.zeros(max(k, 1), POSE_SCORE)
+        idx = np.zeros(max(k, 1), np.int64)
+        n = _I64()
+        _check(lib().fbr_pose_search(self._h, ctypes.byref(sp), ptr(corner) if len(corner) else None, len(corner),
+                                     ptr(surf) if len(surf) else None, len(surf), ptr(seeds) if len(seeds) else None,
+                                     len(seeds), ctypes.byref(lattice), int(top_k), ptr(poses), ptr(sc), ptr(idx),
+                                     ctypes.byref(n)), "fbr_pose_search")
+        return poses[:n.value].copy(), sc[:n.value].copy(), idx[:n.value].copy()
+
+    def relocalize_search(self, points, seeds=None, k=4, sc=None, lattice=None, top=3, score=None):
+        """Find the pose of one raw scan (POINT_XYZIRT) from coarse seeds: project, extract features,
+        down-sample them at the two mapping leaves, take the seed poses from the argument ([n, 6]) or
+        from sc_query's k hypotheses (seeds None), pose_search the lattice around them (default: x, y
+        +-3 m in 0.5 m steps, yaw +-0.8 rad in 0.1 rad steps), register from each of the `top` best
+        poses and score every registered pose again.  Returns (hypotheses, winner): hypotheses =
+        [(searched pose, pose, stats, score)], score the POSE_SCORE record of the registered pose, and
+        winner = the index of the converged, non-degenerate result with the smallest fitness (the
+        first of equals), or -1."""
+        f = self.features(points)
+        corner = self.voxel_grid(f["corner"], self.params.mapping_corner_leaf_size)
+        surf = self.voxel_grid(f["surf"], self.params.mapping_surf_leaf_size)
+        if seeds is None:
+            seeds = [m["pose_guess"] for m in self.sc_query(corner, surf, k, sc)]
+        seeds = np.asarray(seeds, np.float32).reshape(-1, 6)
+        lat = lattice if lattice is not None else pose_lattice((3.0, 3.0, 0.0, 0.8), (0.5, 0.5, 0.0, 0.1))
+        found, _, _ = self.pose_search(corner, surf, seeds, lat, top, score)
+        hyps, winner = [], -1
+        for start in found:
+            pose, st = self.register(f["corner"], f["surf"], start)
+            hyps.append((start, pose, st))
+        scores = self.score_poses(corner, surf, [h[1] for h in hyps], score) if hyps else []
+        hyps = [h + (s,) for h, s in zip(hyps, scores)]
+        for i, (_, _, st, s) in enumerate(hyps):
+            if st["status"] == 0 and st["converged"] and not st["degenerate"] and (
+                    winner < 0 or s["fitness"] < hyps[winner][3]["fitness"]):
+                winner = i
         return hyps, winner
 
     @property

@@ -11,6 +11,7 @@
 //   fbr_sc.hip      scan-context place recognition: descriptor store, search, loop closure under drift
 //   fbr_pg.hip      pose graph: the factor list, the Levenberg-Marquardt driver, correctPoses
 //   fbr_gmap.hip    global map: build from the keyframe store, get, install, save
+//   fbr_score.hip   pose scoring: a scan against the map at many poses, the lattice search
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -499,6 +500,15 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   Dev<float4> d_inst_c, d_inst_s;
   int64_t inst_c_n = 0, inst_s_n = 0;
   bool map_host_stale = false;
+
+  // ---- pose scoring (fbr_score.hip) ----
+  // Scratch of fbr_score_poses / fbr_pose_search, grown on demand; but for the scan's clouds it is
+  // sized by the poses of one launch (fbr_score_params.pose_chunk), not by the call's.
+  GrowDev<float4> d_score_cloud;              // the scan's clouds, corner then surf
+  GrowDev<float> d_score_T;                   // [chunk][kScorePose]
+  GrowDev<ScorePartial> d_score_partial;      // [chunk][work items of a pose]
+  GrowDev<fbr_pose_score> d_score_out;        // [chunk]
+  GrowDev<unsigned long long> d_score_keys;   // [chunk][n_corner + n_surf], calls that ask for the keys
 
   // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;

@@ -520,6 +520,30 @@ void launch_sc_norms(hipStream_t s, const uint32_t* desc, int64_t nslots, int n_
 void launch_sc_search(hipStream_t s, const uint32_t* qdesc, const double* qnorm, const uint32_t* desc, const double* norms,
                       int64_t n, int n_ring, int n_sector, ScRec* rec);
 
+// ---- pose scoring (k_score.hip) ----
+constexpr int kScorePose = 18;  // floats per pose: rows 0-2 of its affine (12), the crop box min, max
+struct ScorePartial {           // one work item (pose, class, block of 256 points)
+  double sum;                   // the inliers' d2
+  int32_t n_in, pad;
+};
+struct ScoreArgs {
+  const float4* corner;         // [nc] the scan's clouds, scan frame
+  const float4* surf;           // [ns]
+  int32_t nc, ns;
+  int32_t n_poses;              // poses of this launch
+  int32_t ipc, ipp;             // work items of a pose's corner points / of all its points
+  const float* T;               // [n_poses][kScorePose]
+  MapGrid mc, ms;
+  int32_t R, RX;                // cells covering 1 m along y, z / along x
+  float g2;                     // fl(gate * gate) <= 1
+  int32_t use_crop;
+  ScorePartial* partial;        // [n_poses][ipp]
+  unsigned long long* keys;     // [n_poses][nc + ns] or null: (d2 bits << 32) | map index, ~0 = no inlier
+  fbr_pose_score* out;          // [n_poses]
+};
+void launch_score_nn(hipStream_t s, const ScoreArgs& a);
+void launch_score_sum(hipStream_t s, const ScoreArgs& a);
+
 // ---- pose graph (k_posegraph.hip; the arithmetic is fbr_pg.h's) ----
 struct PgState {
   double cost[2];      // F of the linearised poses / of the trial poses

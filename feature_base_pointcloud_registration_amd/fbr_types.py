@@ -205,6 +205,37 @@ def gmap_params(**kw):
     return p
 
 
+# pose scoring (include/fbr.h "pose scoring")
+FBR_POSE_SEARCH_MAX = 1 << 20
+
+
+class FbrScoreParams(_Dictable):
+    _fields_ = [("gate", ctypes.c_float), ("use_crop", ctypes.c_int32), ("pose_chunk", ctypes.c_int32),
+                ("reserved_", ctypes.c_int32 * 5)]
+
+
+class FbrPoseLattice(_Dictable):
+    _fields_ = [("half", ctypes.c_float * 4), ("step", ctypes.c_float * 4)]
+
+
+# fbr_pose_score as a record array: one per pose
+POSE_SCORE = np.dtype([("n", np.int32, 2), ("n_in", np.int32, 2), ("sum_d2", np.float64, 2), ("fitness", np.float64)])
+assert POSE_SCORE.itemsize == 40
+
+
+def score_params(**kw):
+    """fbr_score_params_default: gate 1 m, registration's crop box, pose_chunk 0 (1024 poses per launch)."""
+    p = FbrScoreParams(1.0, 1, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def pose_lattice(half=(0.0, 0.0, 0.0, 0.0), step=(0.0, 0.0, 0.0, 0.0)):
+    """fbr_pose_lattice over x, y, z (m) and yaw (rad): offsets i * step for |i| <= floor(half / step)."""
+    return FbrPoseLattice((ctypes.c_float * 4)(*half), (ctypes.c_float * 4)(*step))
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

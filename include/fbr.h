@@ -516,6 +516,81 @@ int fbr_sc_detect_loop_closure(fbr_ctx* ctx, double stamp, const fbr_loop_params
 int fbr_perform_loop_closure_sc(fbr_ctx* ctx, double stamp, const fbr_loop_params* lp, const fbr_sc_params* sp,
                                 fbr_loop_result* out, fbr_sc_match* match);
 
+/* ---- pose scoring: one scan against the registration map at many poses -------------
+ * How well a scan fits the map at a pose, as a number, for thousands of poses in one launch: the
+ * quality figure fbr_reg_stats lacks, and the way to use a coarse seed (a GPS fix, an old pose, a
+ * place match a metre off) from which fbr_register converges to nothing.  fbr_pose_search scores a
+ * lattice of hypotheses around the seeds; the caller registers from the few best.
+ *
+ * The score of a pose [roll, pitch, yaw, x, y, z] against the installed map (fbr_set_map,
+ * fbr_load_map, fbr_global_map_install); the clouds are taken as given, in the scan frame (callers
+ * pass the mapping-leaf down-samples, as for fbr_sc_query):
+ *   T = rows 0-2 of fbr_affine_from_pose(pose); q = T p as pointAssociateToMap writes it, float,
+ *   ((T0 px + T1 py) + T2 pz) + T3 per coordinate, every step rounded, no contraction.
+ *   A corner point searches the corner map, a surf point the surf map.  use_crop = 1: only the map
+ *   points inside registration's inclusive box [(-h) + t, h + t] (float, h = fbr_params.crop_half,
+ *   t = the pose's translation) count, what fbr_register from that pose would see; use_crop = 0 (and
+ *   a keyframe local map, which registration does not crop): the whole map.
+ *   d2 = float, flann::L2_Simple's order: d = dx dx; d += dy dy; d += dz dz.  The correspondence of
+ *   q is the smallest key (bits(d2) << 32) | map index over those points, so the lowest map index
+ *   among equal distances; the point is an inlier iff d2 < g2 = fl(gate * gate).  A non-finite q, or
+ *   one with no such point in reach, has no correspondence.
+ *   n[k] = the class's points (0 corner, 1 surf), n_in[k] its inliers, sum_d2[k] the inliers' d2,
+ *   each widened to double;
+ *   fitness = ((sum_d2[0] + sum_d2[1]) + (n_total - n_in_total) * (double)g2) / n_total in double,
+ *   DBL_MAX when n_total = 0: a truncated mean, so that a pose with three good matches cannot beat
+ *   one with three thousand.
+ * 0 < gate <= 1 (the map grid's cell window covers a 1 m radius, the reach the Gauss-Newton search
+ * relies on); anything else, a negative pose_chunk or use_crop outside {0, 1}: FBR_ERR_INVALID_ARG.
+ *
+ * The bytes of a pose's record depend on the pose, the clouds and the map alone: not on the run, on
+ * the other poses of the call or on pose_chunk (a fixed summation tree per block of 256 points, the
+ * blocks added in order, no float or double atomics).  Poses are processed pose_chunk at a time, so
+ * the context's scratch does not grow with n_poses.  Neither call changes the map, the keyframe
+ * store or the stream state. */
+typedef struct fbr_score_params {
+  float gate;          /* 1.0 m */
+  int32_t use_crop;    /* 1 */
+  int32_t pose_chunk;  /* poses per launch; 0 = 1024 */
+  int32_t reserved_[5];
+} fbr_score_params;
+
+typedef struct fbr_pose_score {
+  int32_t n[2];      /* corner, surf points */
+  int32_t n_in[2];   /* ... of them inliers */
+  double sum_d2[2];
+  double fitness;
+} fbr_pose_score;
+
+typedef struct fbr_pose_lattice {
+  float half[4];  /* x, y, z (m), yaw (rad): the offsets reach +- half ... */
+  float step[4];  /* ... in multiples of step */
+} fbr_pose_lattice;
+
+#define FBR_POSE_SEARCH_MAX ((int64_t)1 << 20)  /* hypotheses of one fbr_pose_search */
+
+void fbr_score_params_default(fbr_score_params* p);
+/* scores_out [n_poses]; nn_keys_out (optional, tests and diagnostics): [n_poses][n_corner + n_surf],
+ * corner points first, the correspondence key of every inlier and ~0 for the other points.  Null
+ * or negative arguments: FBR_ERR_INVALID_ARG; no installed map: FBR_ERR_STATE; n_poses = 0 succeeds
+ * and writes nothing. */
+int fbr_score_poses(fbr_ctx* ctx, const fbr_score_params* sp, const fbr_point_xyzi* corner, int64_t n_corner,
+                    const fbr_point_xyzi* surf, int64_t n_surf, const float* poses, int64_t n_poses,
+                    fbr_pose_score* scores_out, uint64_t* nn_keys_out);
+/* Scores the lattice of hypotheses around n_seeds seed poses [n_seeds][6] and returns the
+ * min(top_k, hypotheses) best.  The hypotheses are generated on the host: per axis the offsets are
+ * i * step (float) for |i| <= floorf(half / step) (float division); an axis with step = 0 or
+ * half = 0 has the single offset 0.  x, y, z are added to the seed's translation and yaw to its yaw,
+ * in float.  Order: seed-major, then yaw, z, y, x with x fastest, every axis ascending.  More than
+ * FBR_POSE_SEARCH_MAX hypotheses, a negative or non-finite half or step: FBR_ERR_INVALID_ARG.  All
+ * hypotheses are scored; the top_k smallest by (fitness, hypothesis index) are returned ascending:
+ * poses_out [top_k][6], scores_out [top_k] (optional), index_out [top_k] (optional: the hypothesis
+ * indices), *n_out = how many.  Errors as fbr_score_poses; n_seeds = 0 or top_k = 0: *n_out = 0. */
+int fbr_pose_search(fbr_ctx* ctx, const fbr_score_params* sp, const fbr_point_xyzi* corner, int64_t n_corner,
+                    const fbr_point_xyzi* surf, int64_t n_surf, const float* seeds, int64_t n_seeds,
+                    const fbr_pose_lattice* lattice, int64_t top_k, float* poses_out, fbr_pose_score* scores_out,
+                    int64_t* index_out, int64_t* n_out);
+
 /* ---- pose graph: key poses from odometry, loop and GPS factors ----------------------
  * The reference's addOdomFactor (:1517-1541), addGPSFactor (:1543-1634), the loop BetweenFactor
  * (:743-758) and correctPoses (:1735-1770), as a batch optimiser over the keyframe store, so that

@@ -362,6 +362,46 @@ class MapOptimization {
     return r;
   }
 
+  /* Pose scoring (include/fbr.h, "pose scoring"): how well mapping-leaf down-sampled scan-frame
+   * features fit the installed map at each of n poses [roll, pitch, yaw, x, y, z], and the best
+   * top_k poses of a lattice of hypotheses around coarse seeds, each to be tried with registration(). */
+  std::vector<fbr_pose_score> scorePoses(const fbr_score_params& sp, const std::vector<fbr_point_xyzi>& corner,
+                                         const std::vector<fbr_point_xyzi>& surf, const std::vector<float>& poses,
+                                         std::vector<uint64_t>* nn_keys = nullptr) {
+    const int64_t n = (int64_t)poses.size() / 6;
+    std::vector<fbr_pose_score> out((size_t)n);
+    if (nn_keys) nn_keys->assign((size_t)n * (corner.size() + surf.size()), ~(uint64_t)0);
+    check(fbr_score_poses(c_.get(), &sp, corner.data(), (int64_t)corner.size(), surf.data(), (int64_t)surf.size(),
+                          poses.data(), n, out.data(), nn_keys ? nn_keys->data() : nullptr),
+          "fbr_score_poses");
+    return out;
+  }
+  struct PoseHypothesis {
+    float pose[6];
+    fbr_pose_score score;
+    int64_t index;  // in the lattice's order
+  };
+  std::vector<PoseHypothesis> poseSearch(const fbr_score_params& sp, const std::vector<fbr_point_xyzi>& corner,
+                                         const std::vector<fbr_point_xyzi>& surf, const std::vector<float>& seeds,
+                                         const fbr_pose_lattice& lattice, int64_t top_k) {
+    const size_t cap = (size_t)(top_k > 0 ? top_k : 1);
+    std::vector<float> poses(cap * 6);
+    std::vector<fbr_pose_score> scores(cap);
+    std::vector<int64_t> index(cap);
+    int64_t n = 0;
+    check(fbr_pose_search(c_.get(), &sp, corner.data(), (int64_t)corner.size(), surf.data(), (int64_t)surf.size(),
+                          seeds.data(), (int64_t)seeds.size() / 6, &lattice, top_k, poses.data(), scores.data(),
+                          index.data(), &n),
+          "fbr_pose_search");
+    std::vector<PoseHypothesis> out((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+      for (int k = 0; k < 6; ++k) out[(size_t)i].pose[k] = poses[(size_t)i * 6 + k];
+      out[(size_t)i].score = scores[(size_t)i];
+      out[(size_t)i].index = index[(size_t)i];
+    }
+    return out;
+  }
+
   /* Pose graph (include/fbr.h, "pose graph"): the factors of saveKeyFramesAndFactor (addOdomFactor
    * :1517-1541, addGPSFactor :1543-1634, the loop BetweenFactor :743-758), a batch optimise in place
    * of isam->update, and correctPoses (:1735-1770) for a host without GTSAM. */
