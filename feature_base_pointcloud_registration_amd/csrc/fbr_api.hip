@@ -189,23 +189,18 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
               dalloc(c->d_nsame, (int64_t)c->max_items * 256) ||
               dalloc(c->d_iter_cnt, kMaxSub * 4 * std::max(1, p->max_iterations)) ||
               dalloc(c->d_feat_scratch, Bw * H * feat_slot_bytes(c->W)) ||
-              dalloc(c->h_iter_flags, kMaxSub * (std::max(1, p->max_iterations) + 1)) ||
-              hipHostGetDevicePointer((void**)&c->d_iter_flags, c->h_iter_flags, 0) != hipSuccess || dalloc(c->d_pose_out, Bw * 6) ||
+              c->iter_flags.alloc(kMaxSub * (std::max(1, p->max_iterations) + 1)) || dalloc(c->d_pose_out, Bw * 6) ||
               dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6 + 12) ||
               dalloc(c->d_desk_mode, B) || dalloc(c->d_rowmin, Bw * H) || dalloc(c->d_result, B) ||
               dalloc(c->d_choff, Bw * H * (c->W / 32 + 1)) ||
               dalloc(c->h_result, B) || dalloc(c->h_scan, c->NMAX) || dalloc(c->h_nin, 1) || dalloc(c->h_crop, 2) ||
-              dalloc(c->h_guess, 6) || dalloc(c->h_direct, 1) ||
-              hipHostGetDevicePointer((void**)&c->d_direct, c->h_direct, 0) != hipSuccess ||
-              dalloc(c->d_direct_done, 1);
+              dalloc(c->h_guess, 6) || c->direct.alloc(1) || dalloc(c->d_direct_done, 1);
   if (fail) {
     fbr_destroy(c);
     return FBR_ERR_HIP;
   }
   c->d_pts = c->d_pts_own;
   c->knn_desc.assign((size_t)std::max(1, p->max_iterations), KnnLaunchDesc{});
-  std::memset(c->h_iter_flags, 0, sizeof(unsigned long long) * kMaxSub * (std::max(1, p->max_iterations) + 1));
-  std::memset(c->h_direct, 0, sizeof(JobResult));
   if (hipMemset(c->d_sstream, 0, sizeof(StreamState)) != hipSuccess ||
       hipMemset(c->d_label_stream, 0, HW) != hipSuccess || hipMemset(c->d_col, 0, sizeof(int32_t) * Bw * HW) != hipSuccess ||
       hipMemset(c->d_range, 0, sizeof(float) * Bw * HW) != hipSuccess ||

@@ -166,9 +166,7 @@ int fbr_batch_launch(fbr_ctx* c) {
   // return once launch n - (nslot - 1) is fully enqueued (its slot is launch_seq mod nslot now that
   // launch_seq = n + 1; nslot = 1: this launch itself)
   if (!rc) rc = advance_runs(c, (int)(c->launch_seq % c->nslot));
-  debug_counters().batch_ns[0].fetch_add(
-      std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(),
-      std::memory_order_relaxed);
+  debug_counters().batch_ns[0].fetch_add(ns_since(t0), std::memory_order_relaxed);
   return rc;
 }
 
@@ -214,7 +212,7 @@ int fbr_batch_labels(fbr_ctx* c, int job, int8_t* label, int64_t cap, int64_t* n
   const int64_t w = (int64_t)c->last_slot * c->Bcap + job;
   CK(fbr_sync(c->stream));
   for (const GnRun& r : c->run)
-    for (int k = 0; k < r.nsub; ++k) CK(fbr_sync(r.subs[k].st));
+    for (int k = 0; k < r.nsub; ++k) CK(fbr_sync(r.s[k].sub.st));
   int32_t nv = 0;
   CK(hipMemcpy(&nv, c->d_nvalid + w, sizeof(int32_t), hipMemcpyDeviceToHost));
   *n_out = nv;
@@ -251,8 +249,8 @@ int fbr_batch_export_ready(fbr_ctx* c, void* device_dst, void* wait_stream, void
       s = q;
   if (s < 0 || c->run[s].pending) return FBR_OK;
   const GnRun& r = c->run[s];
-  hipStream_t st = r.subs[0].st;
-  for (int k = 1; k < r.nsub; ++k) CK(hipStreamWaitEvent(st, c->xev[r.subs[k].k], 0));
+  hipStream_t st = r.s[0].sub.st;
+  for (int k = 1; k < r.nsub; ++k) CK(hipStreamWaitEvent(st, c->xev[r.s[k].sub.k], 0));
   if (wait_stream) {  // the caller's previous reader of device_dst
     CK(hipEventRecord(c->ev_ext, (hipStream_t)wait_stream));
     CK(hipStreamWaitEvent(st, c->ev_ext, 0));

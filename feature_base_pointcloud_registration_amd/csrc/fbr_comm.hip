@@ -174,8 +174,8 @@ int batch_allgather(fbr_ctx* c, fbr_comm* m, int64_t launch_id, void* recv, void
   int rc = advance_runs(c, s);  // the launch fully enqueued (the host follows its GN flags)
   if (rc) return rc;
   const GnRun& r = c->run[s];
-  hipStream_t st = r.subs[0].st;
-  for (int k = 1; k < r.nsub; ++k) CK(hipStreamWaitEvent(st, c->xev[r.subs[k].k], 0));
+  hipStream_t st = r.s[0].sub.st;
+  for (int k = 1; k < r.nsub; ++k) CK(hipStreamWaitEvent(st, c->xev[r.s[k].sub.k], 0));
   if (m->used) CK(hipStreamWaitEvent(st, m->done, 0));  // the previous gather (maybe another stream)
   if (wait_stream) {  // the caller's reads of the previous result out of recv
     CK(hipEventRecord(m->ev_wait, (hipStream_t)wait_stream));

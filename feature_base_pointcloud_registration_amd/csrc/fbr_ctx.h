@@ -2,7 +2,7 @@
 // fbr_ctx, the small helpers every unit uses, and the few functions that cross units.
 //
 //   fbr_api.hip     life cycle (fbr_create's allocations, the drain before ~fbr_ctx), profiling timers, diagnostics
-//   fbr_stages.hip  per-stage launch glue, the Gauss-Newton run driver and its flag waits, results
+//   fbr_stages.hip  per-stage launch glue, the Gauss-Newton run driver, results
 //   fbr_scan.hip    single-scan entry points, their upload path and copy-worker pool
 //   fbr_batch.hip   batch stage / launch / export state machine, the pinned-ring ingest
 //   fbr_comm.hip    RCCL communicator and pose gather
@@ -12,6 +12,11 @@
 //   fbr_pg.hip      pose graph: the factor list, the Levenberg-Marquardt driver, correctPoses
 //   fbr_gmap.hip    global map: build from the keyframe store, get, install, save
 //   fbr_score.hip   pose scoring: a scan against the map at many poses, the lattice search
+//
+// and the headers free of HIP, each checked on a CPU by a program under tests/native:
+//   fbr_knobs.h     the environment knobs
+//   fbr_own.h       owning handles (HostWord below builds on them)
+//   fbr_pace.h      device-paced host loops: the flag words, the flag wait, run_ahead, gn_plan
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -41,6 +46,7 @@
 #include "fbr_knobs.h"
 #include "fbr_msg.h"
 #include "fbr_own.h"
+#include "fbr_pace.h"
 
 using namespace fbr;
 
@@ -58,8 +64,7 @@ namespace internal __attribute__((visibility("hidden"))) {
 
 // Host wall time since t0 into DebugCounters::host_ns[k] (fbr_diag_host_times).
 inline void host_time(int k, std::chrono::steady_clock::time_point t0) {
-  const auto ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-  debug_counters().host_ns[k].fetch_add((long long)ns, std::memory_order_relaxed);
+  debug_counters().host_ns[k].fetch_add((long long)pace::ns_since(t0), std::memory_order_relaxed);
 }
 
 // Blocking host synchronisations, counted (fbr_debug_counters).
@@ -150,6 +155,26 @@ int dalloc(own::Owned<T, Mem>& p, size_t count) {
   return p.alloc(count) ? FBR_OK : alloc_failed();
 }
 
+// A host-mapped block the device writes and the host polls, zero-filled, with its device address.
+template <typename T>
+class HostWord {
+ public:
+  int alloc(size_t count) {
+    if (!h_.alloc(count)) return alloc_failed();
+    std::memset(h_.get(), 0, sizeof(T) * std::max<size_t>(count, 1));
+    if (hip_ok(hipHostGetDevicePointer((void**)&d_, h_.get(), 0), "hipHostGetDevicePointer")) return FBR_OK;
+    h_.reset();
+    return FBR_ERR_HIP;
+  }
+  explicit operator bool() const { return h_ != nullptr; }
+  T* host() const { return h_; }
+  T* dev() const { return d_; }  // not owning: host()'s device address
+
+ private:
+  Mapped<T> h_;
+  T* d_ = nullptr;
+};
+
 // Grow a device array to hold `need` elements (keeping `keep` of them): own::Growable's rule, with
 // the copy on `st` and its sync as the step the old block has to outlive.
 template <typename T>
@@ -172,6 +197,7 @@ struct KernelTimer {
 }  // namespace internal
 }  // namespace fbr
 using namespace fbr::internal;
+using namespace fbr::pace;
 
 constexpr int kMaxSub = 8;  // sub-batch streams per launch (FBR_NSUB); more than 3 pays only with
                              // GPU_MAX_HW_QUEUES above HIP's default of 4 (one hardware queue per stream)
@@ -225,39 +251,24 @@ struct Sub {
 // `lag` (gn_lag) iterations ahead of each sub-batch and stops once its k_gn_solve reports that no job is
 // active (flags in host-mapped memory), so a launch's tail cannot be enqueued before the device
 // has run most of it; two launches in flight are advanced together (fbr_batch_launch).
+struct GnSubRun {
+  Sub sub;
+  GnArgs a;
+  bool live = false, watch = false, done = false;
+  int active = 0;  // jobs still iterating `lag` iterations ago (an upper bound now)
+  int it = 0;      // next iteration to enqueue
+  FlagWait wait;   // the wait for the flag that iteration needs (a non-blocking pass resumes it)
+};
 struct GnRun {
   bool pending = false;
   bool trace = false;
   int nsub = 0;
   unsigned long long gen = 0;
-  Sub subs[kMaxSub];
-  GnArgs a[kMaxSub];
-  bool live[kMaxSub] = {}, watch[kMaxSub] = {}, done[kMaxSub] = {};
-  int lag = 2;               // gn_lag: iterations enqueued ahead of the latest flag read
-  int active[kMaxSub] = {};  // jobs still iterating `lag` iterations ago (an upper bound now)
-  int it[kMaxSub] = {};      // next iteration to enqueue
-  long polls[kMaxSub] = {};  // unanswered flag reads of the current wait
-  std::chrono::steady_clock::time_point wait0[kMaxSub];  // start of the current wait
-  int64_t next_query[kMaxSub] = {};  // ns into the current wait of the next stream query
+  int lag = 2;  // gn_lag: iterations enqueued ahead of the latest flag read
+  GnSubRun s[kMaxSub];
 };
 
-// A flag wait asks the runtime whether the stream drained (flags not visible although the work
-// is done) only once it has lasted several times longer than the waits of its kind usually do:
-// hipStreamQuery puts a marker into the stream, and a marker between two iterations' kernels cost
-// ~5.7 us on the device (every launch enqueued after a wait had one).  The bound is 4x the
-// smoothed duration of the completed waits of that kind (GN flags of batch runs, of single-scan
-// runs, single-scan direct results), within [kQueryMinNs, kQueryMaxNs]; queries repeat at most
-// every half bound.  (Round 5 used a fixed 2 ms, which a late-visible flag turned into a 2 ms scan.)
-// The floor stays above the longest normal single-scan wait (0.44 ms measured, r06c): at 150 us
-// about one wait per scan queried its stream, and each query is a marker before the next kernel.
-constexpr int64_t kQueryMinNs = 500000, kQueryMaxNs = 2000000;
-struct WaitBound {
-  double ema_ns = 0.0;
-  int64_t after() const {
-    return ema_ns <= 0.0 ? kQueryMaxNs : std::min<int64_t>(kQueryMaxNs, std::max<int64_t>(kQueryMinNs, (int64_t)(4.0 * ema_ns)));
-  }
-  void done(int64_t ns) { ema_ns = ema_ns <= 0.0 ? (double)ns : 0.875 * ema_ns + 0.125 * (double)ns; }
-};
+// The kinds of flag wait, each with a bound of its own (fbr_pace.h WaitBound).
 enum { kWaitBatchFlag = 0, kWaitScanFlag = 1, kWaitDirect = 2 };
 
 // Members stand under the unit that owns them: the unit that gives them their meaning and, but for
@@ -348,8 +359,7 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   Dev<int32_t> d_fb_list;  // [3][max_items][256] queued / binned query slots, query blocks
   Dev<int32_t> d_bin;      // [kMaxSub][3][bin_nb] per-block counts, cursors, non-empty list
   int64_t bin_nb = 0, bin_nb_c = 0;
-  Mapped<unsigned long long> h_iter_flags;     // host-mapped, written by k_gn_solve
-  unsigned long long* d_iter_flags = nullptr;  // not owning: h_iter_flags' device address
+  HostWord<unsigned long long> iter_flags;  // written by k_gn_solve: [kMaxSub][max_iterations], then [kMaxSub] item counts
   unsigned long long gn_gen = 0;
   Dev<int32_t> d_iter_cnt;
   WaitBound wait_bound[3];            // kWaitBatchFlag / kWaitScanFlag / kWaitDirect
@@ -386,13 +396,12 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   GrowDev<uint8_t> d_msg;          // raw PointCloud2 bytes of the last *_msg call (grown on demand)
   GrowPinned<uint8_t> h_msg;       // staging of raw PointCloud2 bytes (grown on demand)
   // fbr_process_scan's direct result (GnArgs::direct): the ending k_gn_solve packs the job's
-  // result into h_direct (host-mapped); the host spins on its generation word instead of
+  // result into `direct` (host-mapped); the host spins on its generation word instead of
   // enqueueing finalize + pack + copy and synchronising.  The no-op iterations the host had
   // enqueued ahead of the last flag may still be queued when the call returns (tail_pending):
   // the next single-scan call is ordered after them on the stream, every other entry point
   // synchronises the stream first (enter).
-  Mapped<JobResult> h_direct;
-  JobResult* d_direct = nullptr;  // not owning: h_direct's device address
+  HostWord<JobResult> direct;
   Dev<int32_t> d_direct_done;
   int32_t direct_gen = 0;     // generation of the current single-scan run (0: direct off)
   int32_t direct_gen_seq = 0;
@@ -448,8 +457,7 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   GrowDev<double> d_icp_partial;
   GrowDev<KfSeg> d_icp_segs;
   Dev<IcpState> d_icp_state;   // the state, then the fbr_icp_result record
-  Mapped<unsigned long long> h_icp_flag;     // host-mapped stop word, written by k_icp_solve
-  unsigned long long* d_icp_flag = nullptr;  // not owning: h_icp_flag's device address
+  HostWord<unsigned long long> icp_flag;  // the progress word k_icp_solve writes (allocated on first use)
   unsigned long long icp_gen = 0;
   DevGrid icp_grid;            // the ICP's own grid over its target
 
@@ -477,8 +485,7 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   GrowDev<int32_t> d_pg_adj;       // the two adjacency lists: offsets, then entries
   GrowDev<double> d_pg_work;       // every double array of an optimise (fbr_pg.hip pg_prepare)
   Dev<PgState> d_pg_state;
-  Mapped<unsigned long long> h_pg_flag;     // host-mapped progress word, written by k_pg_decide
-  unsigned long long* d_pg_flag = nullptr;  // not owning: h_pg_flag's device address
+  HostWord<unsigned long long> pg_flag;  // the progress word k_pg_decide writes (allocated on first use)
   unsigned long long pg_gen = 0;
   // marginal covariances (fbr_pg_marginals): valid for the result above while the factor count is
   // the one that optimise saw

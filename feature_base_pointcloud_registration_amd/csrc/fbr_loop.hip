@@ -49,11 +49,7 @@ int icp_prepare(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt
   if (!rc) rc = grow(c->d_icp_partial, std::max<int64_t>(nblk, 1) * kIcpSums, 0, c->stream);
   if (rc) return rc;
   if (!c->d_icp_state && !c->d_icp_state.alloc_bytes(sizeof(IcpState) + sizeof(fbr_icp_result))) return alloc_failed();
-  if (!c->h_icp_flag) {
-    if (dalloc(c->h_icp_flag, 1)) return FBR_ERR_HIP;
-    *c->h_icp_flag = 0;
-    CK(hipHostGetDevicePointer((void**)&c->d_icp_flag, c->h_icp_flag, 0));
-  }
+  if (!c->icp_flag && c->icp_flag.alloc(1)) return FBR_ERR_HIP;
   *a = IcpArgs{};
   a->src = d_src;
   a->x = c->d_icp_x;
@@ -65,7 +61,7 @@ int icp_prepare(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt
   a->far_cnt = c->d_icp_far + ns;
   a->partial = c->d_icp_partial;
   a->st = c->d_icp_state;
-  a->flag = c->d_icp_flag;
+  a->flag = c->icp_flag.dev();
   a->gate2 = INFINITY;
   // cubic cells of the power of two at or above the hint; doubled while outliers would make the
   // box sparse or mostly empty, and without a grid (every query brute force) if that does not end
@@ -103,21 +99,9 @@ int icp_run(fbr_ctx* c, const float4* d_src, int64_t ns, const float4* d_tgt, in
   const double md = (double)ip.max_correspondence_distance;
   a.gate2 = md * md;
   const unsigned long long gen = (++c->icp_gen) & 0xFFFFFFFFull;
-  const volatile unsigned long long* flag = c->h_icp_flag;
   constexpr int kLead = 4;  // iterations the host may run ahead of the device
   for (int it = 0; it < std::max(1, ip.max_iterations); ++it) {
-    bool stopped = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const unsigned long long w = *flag;
-      debug_counters().flag_polls.fetch_add(1, std::memory_order_relaxed);
-      const bool mine = (w >> 32) == gen;
-      stopped = mine && (w & 1);
-      const int seen = mine ? (int)((w & 0xFFFFFFFFull) >> 1) : 0;
-      if (stopped || it - seen <= kLead) break;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;  // enqueue anyway
-    }
-    if (stopped) break;
+    if (run_ahead(c->icp_flag.host(), gen, it, kLead, debug_counters().flag_polls)) break;
     TIMED(c, "icp_nn", launch_icp_nn(c->stream, a, 0, it == 0));
     TIMED(c, "icp_nn_far", launch_icp_far(c->stream, a, 0));
     TIMED(c, "icp_solve", launch_icp_solve(c->stream, a, ip.max_iterations, ip.transformation_epsilon,

@@ -83,11 +83,7 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
   if (!rc) rc = grow(c->d_pg_fac, std::max<int64_t>(nf, 1), 0, c->stream);
   if (rc) return rc;
   if (!c->d_pg_state && dalloc(c->d_pg_state, 1)) return FBR_ERR_HIP;
-  if (!c->h_pg_flag) {
-    if (dalloc(c->h_pg_flag, 1)) return FBR_ERR_HIP;
-    *c->h_pg_flag = 0;
-    CK(hipHostGetDevicePointer((void**)&c->d_pg_flag, c->h_pg_flag, 0));
-  }
+  if (!c->pg_flag && c->pg_flag.alloc(1)) return FBR_ERR_HIP;
   CK(hipMemcpyAsync(c->d_pg_adj, adj.data(), sizeof(int32_t) * adj.size(), hipMemcpyHostToDevice, c->stream));
   CK(hipMemcpyAsync(c->d_pg_fac, F.data(), sizeof(PgFactor) * nf, hipMemcpyHostToDevice, c->stream));
   CK(hipMemsetAsync(c->d_pg_state, 0, sizeof(PgState), c->stream));
@@ -120,7 +116,7 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
   a.q = take(6 * n);
   a.partial = take(nbmax);
   a.st = c->d_pg_state;
-  a.flag = c->d_pg_flag;
+  a.flag = c->pg_flag.dev();
   a.nlev = nlev;
   int64_t ln = n;
   for (int l = 0; l < nlev; ++l, ln = (ln + 1) / 2) {
@@ -142,23 +138,11 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
 // iterations behind), and iterations enqueued past the stop return at once.
 void pg_pcg(fbr_ctx* c, const PgArgs& a, const fbr_pg_params& P) {
   const unsigned long long gen = (++c->pg_gen) & 0xFFFFFFFFull;
-  const volatile unsigned long long* flag = c->h_pg_flag;
   const double tol2 = P.pcg_rel_tol * P.pcg_rel_tol;
   constexpr int kLead = 4;  // iterations the host may run ahead of the device
   TIMED(c, "pg_pcg", launch_pg_pcg_init(c->stream, a, gen));
   for (int it = 0; it < P.max_pcg_iterations; ++it) {
-    bool stopped = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const unsigned long long w = *flag;
-      debug_counters().flag_polls.fetch_add(1, std::memory_order_relaxed);
-      const bool mine = (w >> 32) == gen;
-      stopped = mine && (w & 1);
-      const int seen = mine ? (int)((w & 0xFFFFFFFFull) >> 1) : 0;
-      if (stopped || it - seen <= kLead) break;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;  // enqueue anyway
-    }
-    if (stopped) break;
+    if (run_ahead(c->pg_flag.host(), gen, it, kLead, debug_counters().flag_polls)) break;
     TIMED(c, "pg_pcg", launch_pg_pcg_iter(c->stream, a, it, P.max_pcg_iterations, tol2, gen));
   }
 }

@@ -66,9 +66,7 @@ class CopyPool {
         for (int k = 0; g == seen; ++k) {
           __builtin_ia32_pause();
           g = gen_.load();
-          if ((k & 255) == 255 &&
-              std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count() > spin)
-            break;
+          if ((k & 255) == 255 && ns_since(t0) > spin) break;
         }
       }
       if (g == seen) {

@@ -1,5 +1,5 @@
 // fbr_stages.hip — the device pipeline's host side: the launch glue of each stage, the
-// Gauss-Newton run driver with its flag-wait policy, and the copy of the results.
+// Gauss-Newton run driver (its flag wait and launch plan are fbr_pace.h's), and the copy of the results.
 //
 // One fbr_ctx = one HIP device + one stream + the HBM buffers for a batch of up to max_batch
 // scans.  A batch runs entirely on the device:
@@ -85,8 +85,8 @@ GnArgs gn_args(fbr_ctx* c, const Sub& sb, bool trace) {
   a.fits = c->d_fits + ib * 256;
   a.nsame = c->d_nsame + ib * 256;
   a.fit_cache = knobs::fit_cache();
-  a.iter_flags = c->d_iter_flags + (int64_t)sb.k * mi;
-  a.items_flag = c->d_iter_flags + (int64_t)kMaxSub * mi + sb.k;  // after every sub-batch's iteration flags
+  a.iter_flags = c->iter_flags.dev() + (int64_t)sb.k * mi;
+  a.items_flag = c->iter_flags.dev() + (int64_t)kMaxSub * mi + sb.k;  // after every sub-batch's iteration flags
   a.iter_cnt = c->d_iter_cnt + (int64_t)sb.k * 4 * mi;  // [2 * mi] solve, [mi] queued, [mi] blocks
   if (c->d_bin) {
     const int64_t slots = (int64_t)c->max_items * 256;
@@ -101,8 +101,8 @@ GnArgs gn_args(fbr_ctx* c, const Sub& sb, bool trace) {
   a.desk = c->desk_any ? c->d_desk + sb.in0 : nullptr;
   a.nocrop = c->map_nocrop ? 1 : 0;
   a.deg_carry = sb.stream_mode ? c->stream_degenerate : 0;
-  if (c->direct_gen && sb.stream_mode && sb.B == 1 && c->d_direct) {
-    a.direct = c->d_direct;
+  if (c->direct_gen && sb.stream_mode && sb.B == 1 && c->direct) {
+    a.direct = c->direct.dev();
     a.direct_done = c->d_direct_done;
     a.direct_gen = c->direct_gen;
     a.nvalid = c->d_nvalid + j0;
@@ -116,12 +116,76 @@ GnArgs gn_args(fbr_ctx* c, const Sub& sb, bool trace) {
 }
 
 // The run's work-item count once iteration 0's solve has published it (GnArgs::items_flag), else -1.
-int items_known(fbr_ctx* c, const GnRun& r, int k) {
-  if (!c->h_iter_flags) return -1;
+int items_known(fbr_ctx* c, const GnRun& r, const GnSubRun& s) {
+  if (!c->iter_flags) return -1;
   const int mi = std::max(1, c->P.max_iterations);
-  const volatile unsigned long long* f = c->h_iter_flags + (int64_t)kMaxSub * mi + r.subs[k].k;
+  const volatile unsigned long long* f = c->iter_flags.host() + (int64_t)kMaxSub * mi + s.sub.k;
   const unsigned long long v = *f;
-  return (v >> 32) == (r.gen & 0xFFFFFFFFull) ? (int)(uint32_t)v : -1;
+  return word_of(v, r.gen) ? (int)word_count(v) : -1;
+}
+
+// The flag s.it needs, k_gn_solve's count of `lag` iterations before.  *ready: it is visible
+// (block: wait for it); then s.active is that count, and s.live is cleared at 0.
+int await_flag(fbr_ctx* c, const GnRun& r, GnSubRun& s, bool block, bool* ready) {
+  const Sub& sb = s.sub;
+  const int mi = std::max(1, c->P.max_iterations), i = s.it - r.lag;
+  WaitBound& bound = c->wait_bound[sb.stream_mode ? kWaitScanFlag : kWaitBatchFlag];
+  volatile unsigned long long* f = c->iter_flags.host() + (int64_t)sb.k * mi + i;
+  unsigned long long v = *f;
+  const auto tspin = std::chrono::steady_clock::now();
+  if (s.wait.polls == 0) s.wait.begin(bound, tspin);
+  while (!word_of(v, r.gen)) {
+    if (s.wait.query_due()) {
+      debug_counters().stream_queries.fetch_add(1, std::memory_order_relaxed);
+      const hipError_t q = hipStreamQuery(sb.st);
+      if (q != hipSuccess && q != hipErrorNotReady) return FBR_ERR_HIP;
+      if (q == hipSuccess && !word_of(v = *f, r.gen)) {
+        // the stream drained but the host-mapped flag is not visible: the solve's count is in
+        // device memory (iter_cnt[2 i]), final once the stream is idle; read it and go on
+        // watching (round 5 enqueued every remaining iteration here)
+        int32_t cnt = 0;
+        if (hipMemcpyAsync(&cnt, s.a.iter_cnt + 2 * i, sizeof(cnt), hipMemcpyDeviceToHost, sb.st) != hipSuccess ||
+            fbr_sync(sb.st) != hipSuccess)
+          return FBR_ERR_HIP;
+        v = pack_count(r.gen, (uint32_t)cnt);
+        debug_counters().flag_fallbacks.fetch_add(1, std::memory_order_relaxed);
+        break;
+      }
+    }
+    if (!block) break;
+    v = *f;
+  }
+  *ready = word_of(v, r.gen);
+  if (*ready) s.wait.finish(bound);  // the wait's duration, from its first poll
+  if (block || *ready || !s.watch) debug_counters().batch_ns[1].fetch_add(ns_since(tspin), std::memory_order_relaxed);
+  if (!*ready) return FBR_OK;  // not yet (non-blocking pass)
+  debug_counters().flag_polls.fetch_add(1, std::memory_order_relaxed);
+  s.active = (int)word_count(v);
+  if (s.active == 0) s.live = false;
+  return FBR_OK;
+}
+
+// Iteration s.it of a sub-batch in the plan's shape: kNN, residual (the batch tail: both in one
+// launch), solve.  In one-item mode 1 the one-item launch and the loop launch behind it are timed
+// apart (rocprof: k_gn_knn / k_gn_loop_*).
+void enqueue_iteration(fbr_ctx* c, const GnRun& r, GnSubRun& s, const GnPlan& p) {
+  const hipStream_t st = s.sub.st;
+  const int it = s.it, part = p.one_mode == 1 ? 1 : 0;
+  GnArgs a1 = s.a;
+  a1.one_item = p.one_mode;
+  a1.rest_grid = p.rest_grid;
+  auto parts = [&](const char* name, auto launch) {
+    a1.one_part = part;
+    TIMED_ON(c, st, name, launch());
+    if (!part) return;
+    a1.one_part = 2;
+    TIMED_ON(c, st, "gn_loop", launch());
+  };
+  parts("gn_knn", [&] { launch_gn_knn(st, a1, p.grid, it, p.fused); });
+  if (!p.fused) parts("gn_residual", [&] { launch_gn_residual(st, a1, p.grid); });  // (whole runs fused: 4 % slower, r06b)
+  if (c->knn_last_valid && it < (int)c->knn_desc.size()) c->knn_desc[it] = knn_launch_desc();  // fbr_diag_knn_last
+  TIMED_ON(c, st, "gn_solve", launch_gn_solve(st, s.a, it, r.gen));
+  s.it = it + 1;
 }
 
 // Enqueue the rest of a run, waiting for its flags.
@@ -144,37 +208,27 @@ int register_iterate(fbr_ctx* c, const Sub* subs, int nsub, bool trace) {
 // A single scan's direct result (GnArgs::direct): spin on its generation word; false when the
 // stream drained without it (then the caller takes the enqueued path).
 int wait_direct(fbr_ctx* c, bool* got) {
-  volatile int32_t* gen = &c->h_direct->pad;
+  volatile int32_t* gen = &c->direct.host()->pad;
   *got = false;
-  const auto t0 = std::chrono::steady_clock::now();
-  int64_t next_query = c->wait_bound[kWaitDirect].after();
-  for (int64_t polls = 1;; ++polls) {
-    if (*gen == c->direct_gen) break;
-    if ((polls & 1023) == 0) {
-      const int64_t waited =
-          std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-      if (waited > next_query) {
-        next_query = waited + std::max<int64_t>(kQueryMinNs, next_query / 2);
-        debug_counters().stream_queries.fetch_add(1, std::memory_order_relaxed);
-        const hipError_t q = hipStreamQuery(c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return FBR_ERR_HIP;
-        if (q == hipSuccess && *gen != c->direct_gen) {  // the caller copies the enqueued results
-          debug_counters().flag_fallbacks.fetch_add(1, std::memory_order_relaxed);
-          wait_stat(waited);
-          return FBR_OK;
-        }
+  WaitBound& bound = c->wait_bound[kWaitDirect];
+  FlagWait w;
+  w.begin(bound, std::chrono::steady_clock::now(), -1);  // phase -1: the clock is read on the 1024th poll, not the 1023rd
+  while (*gen != c->direct_gen) {
+    if (w.query_due()) {
+      debug_counters().stream_queries.fetch_add(1, std::memory_order_relaxed);
+      const hipError_t q = hipStreamQuery(c->stream);
+      if (q != hipSuccess && q != hipErrorNotReady) return FBR_ERR_HIP;
+      if (q == hipSuccess && *gen != c->direct_gen) {  // the caller copies the enqueued results
+        debug_counters().flag_fallbacks.fetch_add(1, std::memory_order_relaxed);
+        wait_stat(w.waited);
+        return FBR_OK;
       }
     }
     __builtin_ia32_pause();
   }
-  {
-    const int64_t waited =
-        std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-    c->wait_bound[kWaitDirect].done(waited);
-    wait_stat(waited);
-  }
+  w.finish(bound);
   std::atomic_thread_fence(std::memory_order_acquire);
-  std::memcpy(c->h_result, (const void*)c->h_direct, sizeof(JobResult));
+  std::memcpy(c->h_result, (const void*)c->direct.host(), sizeof(JobResult));
   *got = true;
   return FBR_OK;
 }
@@ -365,11 +419,8 @@ void gn_run_start(fbr_ctx* c, GnRun& r, const Sub* subs, int nsub, bool trace) {
   r.lag = knobs::gn_lag();
   c->knn_last_valid = nsub == 1 && subs[0].stream_mode && subs[0].B == 1 && subs[0].j0 == 0;
   for (int k = 0; k < nsub; ++k) {
-    r.subs[k] = subs[k];
-    r.a[k] = gn_args(c, subs[k], trace);
-    r.live[k] = true;
-    r.active[k] = subs[k].B;
-    r.watch[k] = c->h_iter_flags != nullptr;
+    r.s[k] = GnSubRun{subs[k], gn_args(c, subs[k], trace), /*live*/ true, /*watch*/ (bool)c->iter_flags, /*done*/ false,
+                      /*active*/ subs[k].B};
   }
 }
 
@@ -377,135 +428,37 @@ void gn_run_start(fbr_ctx* c, GnRun& r, const Sub* subs, int nsub, bool trace) {
 // visible (block: wait for it).  A sub-batch whose jobs all stopped, or that reached
 // max_iterations, gets its transformUpdate.  *progress: something was enqueued.
 int gn_run_pass(fbr_ctx* c, GnRun& r, bool block, bool* progress) {
-  const int mi = std::max(1, c->P.max_iterations);
-  const unsigned long long g32 = r.gen & 0xFFFFFFFFull;
   bool all_done = true;
   for (int k = 0; k < r.nsub; ++k) {
-    if (r.done[k]) continue;
-    const Sub& sb = r.subs[k];
-    const int it = r.it[k];
-    if (r.live[k] && it < c->P.max_iterations && r.watch[k] && it >= r.lag) {
-      volatile unsigned long long* f = c->h_iter_flags + (int64_t)sb.k * mi + (it - r.lag);
-      unsigned long long v = *f;
-      const auto tspin = std::chrono::steady_clock::now();
-      if (r.polls[k] == 0) {
-        r.wait0[k] = tspin;
-        r.next_query[k] = c->wait_bound[sb.stream_mode ? kWaitScanFlag : kWaitBatchFlag].after();
-      }
-      while ((v >> 32) != g32) {
-        if ((++r.polls[k] & 1023) == 1023) {
-          const int64_t waited =
-              std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - r.wait0[k]).count();
-          if (waited > r.next_query[k]) {
-            r.next_query[k] = waited + std::max<int64_t>(kQueryMinNs, r.next_query[k] / 2);
-            debug_counters().stream_queries.fetch_add(1, std::memory_order_relaxed);
-            const hipError_t q = hipStreamQuery(sb.st);
-            if (q != hipSuccess && q != hipErrorNotReady) return FBR_ERR_HIP;
-            if (q == hipSuccess && ((v = *f) >> 32) != g32) {
-              // the stream drained but the host-mapped flag is not visible: the solve's count is in
-              // device memory (iter_cnt[2 i]), final once the stream is idle; read it and go on
-              // watching (round 5 enqueued every remaining iteration here)
-              int32_t cnt = 0;
-              if (hipMemcpyAsync(&cnt, r.a[k].iter_cnt + 2 * (it - r.lag), sizeof(cnt), hipMemcpyDeviceToHost, sb.st) !=
-                      hipSuccess ||
-                  fbr_sync(sb.st) != hipSuccess)
-                return FBR_ERR_HIP;
-              v = (g32 << 32) | (unsigned long long)(uint32_t)cnt;
-              debug_counters().flag_fallbacks.fetch_add(1, std::memory_order_relaxed);
-              break;
-            }
-          }
-        }
-        if (!block) break;
-        v = *f;
-      }
-      if ((v >> 32) == g32) {  // the wait's duration (from its first poll) into the bound and the stats
-        const int64_t waited =
-            std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - r.wait0[k]).count();
-        c->wait_bound[sb.stream_mode ? kWaitScanFlag : kWaitBatchFlag].done(waited);
-        wait_stat(waited);
-      }
-      if (block || (v >> 32) == g32 || !r.watch[k])
-        debug_counters().batch_ns[1].fetch_add(
-            std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tspin).count(),
-            std::memory_order_relaxed);
-      if (r.watch[k] && (v >> 32) != g32) {  // not yet (non-blocking pass)
+    GnSubRun& s = r.s[k];
+    if (s.done) continue;
+    const Sub& sb = s.sub;
+    if (s.live && s.it < c->P.max_iterations && s.watch && s.it >= r.lag) {
+      bool ready = false;
+      const int rc = await_flag(c, r, s, block, &ready);
+      if (rc) return rc;
+      if (!ready) {
         all_done = false;
         continue;
       }
-      r.polls[k] = 0;
-      debug_counters().flag_polls.fetch_add(1, std::memory_order_relaxed);
-      if (r.watch[k]) r.active[k] = (int)(v & 0xFFFFFFFFull);
-      if (r.watch[k] && r.active[k] == 0) r.live[k] = false;
     }
-    if (!r.live[k] || it >= c->P.max_iterations) {
-      if (!r.a[k].direct) TIMED_ON(c, sb.st, "gn_finalize", launch_gn_finalize(sb.st, r.a[k]));
+    if (!s.live || s.it >= c->P.max_iterations) {
+      if (!s.a.direct) TIMED_ON(c, sb.st, "gn_finalize", launch_gn_finalize(sb.st, s.a));
       CK(hipEventRecord(c->xev[sb.k], sb.st));  // the sub-batch's last work (batch_quiesce joins it)
-      r.done[k] = true;
+      s.done = true;
       *progress = true;
       continue;
     }
     all_done = false;
-    const bool tail = knobs::gn_tail_div() > 0 && (int64_t)r.active[k] * knobs::gn_tail_div() <= sb.B;
-    // the batch tail also one item per workgroup (the grid then covers the items of the jobs that
-    // stopped too, which return at once); FBR_GN_TAIL_ONE_ITEM=0: a 1,024-workgroup loop
-    const bool tail_one = tail && !sb.stream_mode && knobs::gn_one_item() && knobs::gn_tail_one_item();
-    int grid = std::max(1, std::min(r.a[k].max_items, tail && !tail_one ? std::min(knobs::gn_grid_cap(), 1024) : knobs::gn_grid_cap()));
-    if (sb.stream_mode && c->items_hint > 0) grid = std::min(grid, std::max(16, 2 * c->items_hint));
-    // one-item launches: one workgroup per item once the count is known (no loop launch), before
-    // that a grid of knobs::gn_one_grid() workgroups and the loop launch behind it
-    // (single scans: once the count is known, iteration 2 on; before that the loop over the
-    // previous scan's grid, so no second launch sits on their critical path)
-    const int nk = knobs::gn_one_item() && (!tail || tail_one || sb.stream_mode) ? items_known(c, r, k) : -1;
-    const bool one = knobs::gn_one_item() && (!tail || tail_one) && (!sb.stream_mode || nk >= 0);
-    int one_mode = 0, rest_grid = 0;
-    if (one) {
-      if (nk >= 0) {
-        grid = std::max(1, nk);
-        one_mode = 2;
-        c->gn_items_hint = nk;  // the next run's first grids
-        c->gn_items_hint_B = sb.B;
-      } else if (c->gn_items_hint > 0 && c->gn_items_hint_B == sb.B) {
-        // a previous run of this many jobs: its count + 25 % + 256, and a small loop launch behind
-        grid = std::max(1, std::min(r.a[k].max_items, c->gn_items_hint + c->gn_items_hint / 4 + 256));
-        one_mode = 1;
-        rest_grid = 64;
-      } else {
-        grid = std::max(1, std::min(r.a[k].max_items, knobs::gn_one_grid()));
-        one_mode = 1;
-      }
+    const GnPlanIn in{knobs::gn_tail_div(), knobs::gn_grid_cap(), knobs::gn_one_grid(), knobs::gn_one_item(),
+                      knobs::gn_tail_one_item(), sb.B, s.active, s.a.max_items, sb.stream_mode, c->items_hint,
+                      c->gn_items_hint, c->gn_items_hint_B};
+    const GnPlan p = gn_plan(in, [&] { return items_known(c, r, s); });
+    if (p.adopt >= 0) {
+      c->gn_items_hint = p.adopt;
+      c->gn_items_hint_B = sb.B;
     }
-    if (tail) {  // kNN and residual in one launch (whole runs fused: 4 % slower at round 6, r06b)
-      GnArgs a1 = r.a[k];
-      a1.one_item = one_mode;
-      a1.rest_grid = rest_grid;
-      // the one-item launch and the loop launch behind it timed apart (rocprof: k_gn_knn / k_gn_loop_*)
-      a1.one_part = one_mode == 1 ? 1 : 0;
-      TIMED_ON(c, sb.st, "gn_knn", launch_gn_knn(sb.st, a1, grid, it, true));
-      if (one_mode == 1) {
-        a1.one_part = 2;
-        TIMED_ON(c, sb.st, "gn_loop", launch_gn_knn(sb.st, a1, grid, it, true));
-      }
-    } else {
-      GnArgs a1 = r.a[k];
-      a1.one_item = one_mode;
-      a1.rest_grid = rest_grid;
-      a1.one_part = one_mode == 1 ? 1 : 0;
-      TIMED_ON(c, sb.st, "gn_knn", launch_gn_knn(sb.st, a1, grid, it, false));
-      if (one_mode == 1) {
-        a1.one_part = 2;
-        TIMED_ON(c, sb.st, "gn_loop", launch_gn_knn(sb.st, a1, grid, it, false));
-        a1.one_part = 1;
-      }
-      TIMED_ON(c, sb.st, "gn_residual", launch_gn_residual(sb.st, a1, grid));
-      if (one_mode == 1) {
-        a1.one_part = 2;
-        TIMED_ON(c, sb.st, "gn_loop", launch_gn_residual(sb.st, a1, grid));
-      }
-    }
-    if (c->knn_last_valid && it < (int)c->knn_desc.size()) c->knn_desc[it] = knn_launch_desc();  // fbr_diag_knn_last
-    TIMED_ON(c, sb.st, "gn_solve", launch_gn_solve(sb.st, r.a[k], it, r.gen));
-    r.it[k] = it + 1;
+    enqueue_iteration(c, r, s, p);
     *progress = true;
   }
   if (all_done) r.pending = false;
@@ -531,9 +484,7 @@ int advance_runs(fbr_ctx* c, int target) {
         if (rc) return rc;
       }
     if (p && waiting) {
-      debug_counters().batch_ns[1].fetch_add(
-          std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tw).count(),
-          std::memory_order_relaxed);
+      debug_counters().batch_ns[1].fetch_add(ns_since(tw), std::memory_order_relaxed);
       waiting = false;
     } else if (!p && !waiting) {
       waiting = true;
@@ -551,7 +502,7 @@ int batch_quiesce(fbr_ctx* c) {
   if (rc) return rc;
   for (int s = 0; s < fbr_ctx::kMaxSlots; ++s)
     for (int k = 0; k < c->run[s].nsub; ++k)
-      if (c->run[s].subs[k].st != c->stream) CK(hipStreamWaitEvent(c->stream, c->xev[c->run[s].subs[k].k], 0));
+      if (c->run[s].s[k].sub.st != c->stream) CK(hipStreamWaitEvent(c->stream, c->xev[c->run[s].s[k].sub.k], 0));
   return FBR_OK;
 }
 

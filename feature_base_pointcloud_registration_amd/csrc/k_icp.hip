@@ -26,6 +26,7 @@
 #include "fbr_common.h"
 #include "fbr_icp_solve.h"
 #include "fbr_kernels.h"
+#include "fbr_pace.h"
 
 namespace fbr {
 
@@ -288,8 +289,8 @@ k_icp_solve(IcpArgs a, int nblk, int max_iter, double teps, double feps, unsigne
   st->stopped = stop;
   if (a.flag) {
     __threadfence_system();
-    __hip_atomic_store(a.flag, (gen << 32) | ((unsigned long long)(uint32_t)st->iterations << 1) | (unsigned)stop,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(a.flag, pace::pack_progress(gen, (uint32_t)st->iterations, (unsigned)stop), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
 

@@ -22,6 +22,7 @@
 
 #include "fbr_common.h"
 #include "fbr_kernels.h"
+#include "fbr_pace.h"
 #include "fbr_pg.h"
 
 namespace fbr {
@@ -198,8 +199,8 @@ k_pg_dot(PgArgs a, const double* __restrict__ u, const double* __restrict__ v) {
 
 __device__ inline void pg_publish(const PgArgs& a, unsigned long long gen) {
   __threadfence_system();
-  __hip_atomic_store(a.flag, (gen << 32) | ((unsigned long long)(uint32_t)a.st->iters << 1) | (unsigned)a.st->stopped,
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __hip_atomic_store(a.flag, pace::pack_progress(gen, (uint32_t)a.st->iters, (unsigned)a.st->stopped), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // After z = M^-1 r and the partials of r . z.  first: the start of a solve (rz0; beta = 0); otherwise

@@ -33,6 +33,7 @@
 // 5 x 16 (neighbours) = 96 B.
 #include "fbr_gn.h"
 #include "fbr_imu.h"
+#include "fbr_pace.h"
 
 namespace fbr {
 
@@ -213,10 +214,10 @@ __global__ void __launch_bounds__(kSolveThreads) k_gn_solve(GnArgs a, int iter_i
         __threadfence_system();
       }
       if (a.items_flag && iter_idx == 0)  // the run's item count, for the host's launch grids
-        __hip_atomic_store(a.items_flag, (gen << 32) | (unsigned long long)(uint32_t)a.nitems[0], __ATOMIC_RELAXED,
+        __hip_atomic_store(a.items_flag, pace::pack_count(gen, (uint32_t)a.nitems[0]), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
-      if (a.iter_flags)
-        __hip_atomic_store(&a.iter_flags[iter_idx], (gen << 32) | (unsigned long long)cnt, __ATOMIC_RELAXED,
+      if (a.iter_flags)  // (cnt sums the jobs' 0 / 1 active words: never negative)
+        __hip_atomic_store(&a.iter_flags[iter_idx], pace::pack_count(gen, (unsigned long long)cnt), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }

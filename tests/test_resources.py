@@ -1,7 +1,9 @@
 """Who releases what the host units allocate: the owning handles of csrc/fbr_own.h.
 
 CPU: tests/native/own_check.cpp instantiates the header over a counting malloc / free policy and
-checks the handle semantics under AddressSanitizer and UBSan, as a stand-alone program.
+checks the handle semantics under AddressSanitizer and UBSan, as a stand-alone program;
+tests/native/pace_check.cpp does the same for csrc/fbr_pace.h, the host loops paced by words in the
+host-mapped blocks (HostWord) these handles own.
 
 GPU: fbr_diag_live_resources counts the device blocks, pinned blocks, streams and events the
 process's contexts and communicators hold.  Each test runs in a child process (no other context
@@ -34,6 +36,23 @@ def test_owning_handles_under_sanitizers():
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "own_check: ok" in r.stdout
+
+
+def test_host_pacing_under_sanitizers():
+    """csrc/fbr_pace.h alone, over a fake clock: both flag words round-trip at their widest; the flag
+    wait reads the clock on every 1024th poll only, queries no earlier than its bound and then no
+    more often than every half bound, and feeds the 0.875 / 0.125 average; run_ahead's lead,
+    generation, stop bit and 2 ms; and the Gauss-Newton launch plan on cases worked out by hand
+    (tail or not, the three one-item modes, both hints, each knob off)."""
+    out_dir = os.path.join(NATIVE, "build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "pace_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-I", CSRC, "-o", exe,
+                           os.path.join(NATIVE, "pace_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "pace_check: ok" in r.stdout
 
 
 def run_child(script, env_set=None):
