@@ -347,10 +347,10 @@ extern "C" int fbr_diag_knn_last(fbr_ctx* c, int32_t* n_corner, int32_t* n_surf,
   if (ncs[0]) CK(fbr_memcpy_sync(pts.data(), c->d_cornerDS, sizeof(float4) * ncs[0], hipMemcpyDeviceToHost));
   if (ncs[1]) CK(fbr_memcpy_sync(pts.data() + ncs[0], c->d_surfDS, sizeof(float4) * ncs[1], hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < n; ++i) {
-    const float4 p = pts[i];
-    queries[3 * i] = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
-    queries[3 * i + 1] = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
-    queries[3 * i + 2] = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+    const float4 q = associate(T, pts[i]);
+    queries[3 * i] = q.x;
+    queries[3 * i + 1] = q.y;
+    queries[3 * i + 2] = q.z;
   }
   for (int64_t i = 0; i < 5 * n; ++i) nbr[i] = -1;
   const int ni = range[1] - range[0];

@@ -37,6 +37,17 @@ constexpr float kGridCell = 1.0f;         // kNN search grid cell (>= sqrt of th
 // and rounding it to float is innocuous for sqrt (53 >= 2*24+2 bits).
 __host__ __device__ inline float sqrt_rn(float x) { return (float)sqrt((double)x); }
 
+// pointAssociateToMap (mapOptmization.h:397-403): T p for the row-major 3x4 affine T, per coordinate
+// three products and three sums from left to right, each rounded; w is p's.
+__host__ __device__ __forceinline__ float4 associate(const float* T, const float4& p) {
+  float4 q;
+  q.x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
+  q.y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
+  q.z = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+  q.w = p.w;
+  return q;
+}
+
 // 64-bit unsigned order through the f64 unit: a u64 below 0x7FF0000000000000 read as a double is a
 // non-negative, non-NaN double (a subnormal below 2^52; the kernels keep f64 denormals), and the
 // order of those doubles is the integers' order, so v_min_f64 / v_max_f64 pick the smaller / larger

@@ -189,118 +189,6 @@ __device__ void jacobi_eigen(float* A, float* W, float* V) {
   }
 }
 
-// Same algorithm on per-lane arrays in LDS, element e of a lane's array at base[e * S] (S = the
-// workgroup size, so lanes of a wave always hit distinct banks).  Data-dependent pivots index
-// LDS directly: no divergence across lanes whose pivots differ (used for the 6x6 degeneracy
-// eigen-decomposition, one job per lane).
-template <int N, int S>
-__device__ void jacobi_eigen_lds(float* A, float* W, float* V, int* indR, int* indC) {
-  const float eps = FLT_EPSILON;
-#define A_(i) A[(i) * S]
-#define V_(i) V[(i) * S]
-#define W_(i) W[(i) * S]
-#define R_(i) indR[(i) * S]
-#define C_(i) indC[(i) * S]
-  for (int i = 0; i < N; i++)
-    for (int j = 0; j < N; j++) V_(i * N + j) = (i == j) ? 1.0f : 0.0f;
-  float mv;
-  for (int k = 0; k < N; k++) {
-    W_(k) = A_((N + 1) * k);
-    if (k < N - 1) {
-      int m = k + 1;
-      mv = fabsf(A_(N * k + m));
-      for (int i = k + 2; i < N; i++) {
-        float val = fabsf(A_(N * k + i));
-        if (mv < val) mv = val, m = i;
-      }
-      R_(k) = m;
-    }
-    if (k > 0) {
-      int m = 0;
-      mv = fabsf(A_(k));
-      for (int i = 1; i < k; i++) {
-        float val = fabsf(A_(N * i + k));
-        if (mv < val) mv = val, m = i;
-      }
-      C_(k) = m;
-    }
-  }
-  const int maxIters = N * N * 30;
-  for (int iters = 0; iters < maxIters; iters++) {
-    int k = 0;
-    mv = fabsf(A_(R_(0)));
-    for (int i = 1; i < N - 1; i++) {
-      float val = fabsf(A_(N * i + R_(i)));
-      if (mv < val) mv = val, k = i;
-    }
-    int l = R_(k);
-    for (int i = 1; i < N; i++) {
-      float val = fabsf(A_(N * C_(i) + i));
-      if (mv < val) mv = val, k = C_(i), l = i;
-    }
-    float p = A_(N * k + l);
-    if (fabsf(p) <= eps) break;
-    float y = (float)((double)(W_(l) - W_(k)) * 0.5);
-    float t = fabsf(y) + cvhypot(p, y);
-    float s = cvhypot(p, t);
-    float c = t / s;
-    s = p / s;
-    t = (p / t) * p;
-    if (y < 0.0f) s = -s, t = -t;
-    A_(N * k + l) = 0.0f;
-    W_(k) -= t;
-    W_(l) += t;
-    float a0, b0;
-#define FBR_ROT(v0, v1) a0 = v0, b0 = v1, v0 = a0 * c - b0 * s, v1 = a0 * s + b0 * c
-    for (int i = 0; i < k; i++) FBR_ROT(A_(N * i + k), A_(N * i + l));
-    for (int i = k + 1; i < l; i++) FBR_ROT(A_(N * k + i), A_(N * i + l));
-    for (int i = l + 1; i < N; i++) FBR_ROT(A_(N * k + i), A_(N * l + i));
-    for (int i = 0; i < N; i++) FBR_ROT(V_(N * k + i), V_(N * l + i));
-#undef FBR_ROT
-    for (int j = 0; j < 2; j++) {
-      int idx = j == 0 ? k : l;
-      if (idx < N - 1) {
-        int m = idx + 1;
-        mv = fabsf(A_(N * idx + m));
-        for (int i = idx + 2; i < N; i++) {
-          float val = fabsf(A_(N * idx + i));
-          if (mv < val) mv = val, m = i;
-        }
-        R_(idx) = m;
-      }
-      if (idx > 0) {
-        int m = 0;
-        mv = fabsf(A_(idx));
-        for (int i = 1; i < idx; i++) {
-          float val = fabsf(A_(N * i + idx));
-          if (mv < val) mv = val, m = i;
-        }
-        C_(idx) = m;
-      }
-    }
-  }
-  for (int k = 0; k < N - 1; k++) {
-    int m = k;
-    for (int i = k + 1; i < N; i++)
-      if (W_(m) < W_(i)) m = i;
-    if (k != m) {
-      float t = W_(m);
-      W_(m) = W_(k);
-      W_(k) = t;
-      for (int i = 0; i < N; i++) {
-        float u = V_(N * m + i);
-        V_(N * m + i) = V_(N * k + i);
-        V_(N * k + i) = u;
-      }
-    }
-  }
-#undef A_
-#undef V_
-#undef W_
-#undef R_
-#undef C_
-}
-
 // LDS writes of this wave visible to all its lanes (no workgroup barrier: the other waves of the
 // workgroup do not take part).
 __device__ __forceinline__ void wave_lds_sync() {

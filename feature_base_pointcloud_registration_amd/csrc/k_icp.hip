@@ -46,15 +46,6 @@ __device__ __forceinline__ void icp_consider(const float4 p, uint32_t id, float 
   }
 }
 
-__device__ __forceinline__ float4 icp_apply(const float* T, const float4 p) {
-  float4 q;
-  q.x = ((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3];
-  q.y = ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7];
-  q.z = ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11];
-  q.w = p.w;
-  return q;
-}
-
 __global__ void k_icp_init(IcpArgs a) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   IcpState* st = a.st;
@@ -70,8 +61,8 @@ __global__ void __launch_bounds__(256) k_icp_nn(IcpArgs a, int mode, int first) 
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
   float4 p = (mode || first) ? a.src[i] : a.x[i];
-  if (mode) p = icp_apply(st->fin, p);
-  else if (!first) p = icp_apply(st->T, p);
+  if (mode) p = associate(st->fin, p);
+  else if (!first) p = associate(st->T, p);
   a.x[i] = p;
   if (!map_point_finite(p)) {  // no correspondence
     a.key[i] = kIcpNone;

@@ -25,13 +25,7 @@ k_kf_transform(const float4* __restrict__ pool, const KfSeg* __restrict__ segs, 
   if (s >= nseg) return;
   const KfSeg g = segs[s];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < g.count; i += (int64_t)gridDim.x * 256) {
-    const float4 p = pool[g.src + i];
-    float4 q;
-    q.x = g.T[0] * p.x + g.T[1] * p.y + g.T[2] * p.z + g.T[3];
-    q.y = g.T[4] * p.x + g.T[5] * p.y + g.T[6] * p.z + g.T[7];
-    q.z = g.T[8] * p.x + g.T[9] * p.y + g.T[10] * p.z + g.T[11];
-    q.w = p.w;
-    out[g.dst + i] = q;
+    out[g.dst + i] = associate(g.T, pool[g.src + i]);
   }
 }
 

@@ -23,7 +23,9 @@
 //                  its own bound box: ~10-30 points instead of ~140, each an LDS read;
 //   k_gn_knn_list  the grid search for the queued queries.
 // Queries of different jobs share a tile, so a job's CropBox is tested per point unless the tile
-// lies inside it (then never).
+// lies inside it (then never).  The keys, the 5-NN list and knn5_grid, which serves the queries
+// left to the grid, are fbr_grid_search.h's; the query's pose and warm-start bound are
+// gn_knn_block's (fbr_gn.h: associate, warm_bound), its result write is restated in bin_write.
 //
 // Exactness.  The scanned set of every query still contains every crop-box point whose computed d2
 // is <= bound: a point with fl(q - p)^2 summed <= bound has |q_x - p_x| <= sqrt(bound) (1 + 2^-22)
@@ -55,7 +57,8 @@ struct BinTileLds {
 __device__ __forceinline__ int fine8(float x) { return (int)floorf(x * kFineInv); }
 
 // The query of slot (it, tid) at the job's current pose and its warm-start bound (the largest
-// distance to its previous 5 neighbours; +inf without them): gn_knn_block's arithmetic.
+// distance to its previous 5 neighbours; +inf without them): gn_knn_block's arithmetic, through the
+// same associate and warm_bound.
 struct BinQuery {
   float x0, y0, z0, bound;
   int32_t oid[5];
@@ -66,10 +69,10 @@ __device__ __forceinline__ void bin_query(const GnArgs& a, int it, int tid, cons
   const int job = item.x;
   const bool corner = item.y == 0;
   const float4 p = corner ? a.cornerDS[job * a.capc + item.z + tid] : a.surfDS[job * a.caps + item.z + tid];
-  const float* T = g.T;
-  q.x0 = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
-  q.y0 = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
-  q.z0 = T[8] * p.x + T[9] * p.y + T[10] * p.z + T[11];
+  const float4 t = associate(g.T, p);
+  q.x0 = t.x;
+  q.y0 = t.y;
+  q.z0 = t.z;
   const int32_t* o = a.nbr + (int64_t)it * 5 * kResThreads + tid;
   q.have_prev = o[0] >= 0;
   q.bound = __int_as_float(0x7f800000);
@@ -77,19 +80,9 @@ __device__ __forceinline__ void bin_query(const GnArgs& a, int it, int tid, cons
   for (int k = 0; k < 5; ++k) q.oid[k] = -1;
   if (q.have_prev) {
     const float4* by_id = corner ? a.mc.by_id : a.ms.by_id;
-    float mx = 0.0f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) q.oid[k] = o[k * kResThreads];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const float4 m = by_id[q.oid[k]];
-      float dist = 0.0f, diff;
-      diff = q.x0 - m.x; dist += diff * diff;
-      diff = q.y0 - m.y; dist += diff * diff;
-      diff = q.z0 - m.z; dist += diff * diff;
-      mx = fmaxf(mx, dist);
-    }
-    q.bound = mx;
+    q.bound = warm_bound(by_id, q.oid, q.x0, q.y0, q.z0);
   }
 }
 

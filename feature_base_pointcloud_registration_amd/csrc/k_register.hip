@@ -18,7 +18,8 @@
 //     correspondence is kept only if the 5th neighbour has d2 < 1.0 (:1027, :1154), keeping the 5
 //     smallest (d2, index) with d2 < 1.0 among the cells within radius 1 selects exactly the same
 //     neighbours as exact kNN-5 on the cropped cloud.  Cells are pruned with a float lower bound
-//     that provably never exceeds a member point's computed distance (see axis_lb).
+//     that provably never exceeds a member point's computed distance (axis_lb, fbr_grid_search.h:
+//     the search is that header's knn5_grid; fbr_gn.h holds the Gauss-Newton step around it).
 //   * k_gn_knn: one lane per query (corner and surf queries of every active job of the batch are
 //     packed into 256-query work items; the mapping-DS clouds are in Morton order, so a wave's
 //     queries are spatially compact); writes the 5 neighbours' map indices per query.

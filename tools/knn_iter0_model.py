@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """CPU cost model of the first Gauss-Newton iteration's kNN (no warm start), to size a two-pass
-design before writing it: a flat walk (fbr_gn.h knn5_grid<.., kFlat>) under a static bound b, exact
+design before writing it: a flat walk (fbr_grid_search.h knn5_grid<.., kFlat>) under a static bound b, exact
 whenever the query's 5th distance is <= b, with the current rank-ordered walk rerun for the lanes
 where it is not.
 

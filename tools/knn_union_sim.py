@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""CPU model of the flat kNN walk's memory pattern (fbr_gn.h knn5_grid<.., kFlat>), to size an
+"""CPU model of the flat kNN walk's memory pattern (fbr_grid_search.h knn5_grid<.., kFlat>), to size an
 LDS-staged design before writing it.
 
 For C2 jobs: the mapping-DS queries in Morton order (the device's order), transformed by the
