@@ -5,8 +5,6 @@
 
 namespace {
 
-int64_t seg_cap(int W) { return W / 6 + 8; }
-
 int64_t feat_slot_bytes(int W) {
   FeatArgs a{};
   feat_caps(W, a);
@@ -56,13 +54,13 @@ void timer_end(hipStream_t st, hipEvent_t ev_end) {
   t = LaunchTimer{};
 }
 
-// LDS / scratch capacities of k_features for a Horizon_SCAN of W.
+// LDS / scratch capacities of k_features for a Horizon_SCAN of W (fbr_feat_layout.h).
 void feat_caps(int W, FeatArgs& a) {
-  a.lcap = W + 16;
-  a.segcap = (int)seg_cap(W);
-  a.kseg = 1;
-  while (a.kseg < a.segcap - 1) a.kseg <<= 1;
-  a.nwcap = (a.lcap + 63) / 64 + 1;
+  const featlay::Caps c = featlay::caps_of(W);
+  a.lcap = c.lcap;
+  a.segcap = c.segcap;
+  a.kseg = c.kseg;
+  a.nwcap = c.nwcap;
   a.gslot_bytes = (int64_t)features_gslot_bytes(a);
 }
 

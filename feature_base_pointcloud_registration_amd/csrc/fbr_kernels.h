@@ -9,6 +9,7 @@
 #include <functional>
 
 #include "fbr_common.h"
+#include "fbr_feat_layout.h"
 #include "fbr_gmap.h"
 #include "fbr_pg.h"
 
@@ -135,11 +136,13 @@ struct FeatArgs {
   float4* corner_slot;   // [B][H][120]
   int32_t* corner_cnt;   // [B][H]
   int32_t* err;          // [B]
+  // featlay::Caps of W (fbr_feat_layout.h, through feat_caps): the kernel's carve and the two size
+  // functions below lay LDS and the scratch slots out from these four
   int lcap, segcap;      // LDS capacities (window length, segment length)
   int kseg;              // segment sort capacity: next power of two >= segcap - 1 (<= 1024)
   int nwcap;             // 64-bit words per window bit array
-  unsigned char* gscratch;  // [B*H][gslot_bytes] sorted-path buffers (stale-slot segment, ties)
-  int64_t gslot_bytes;
+  unsigned char* gscratch;  // [B*H][gslot_bytes] featlay::Slot per ring: sorted_order's buffers, the window's curvature
+  int64_t gslot_bytes;      // featlay::slot_of(...).total
   unsigned long long* stamps;  // diagnostic builds only: [B*H][12] phase cycle sums
   // 0 (independent batch jobs): the surf walk is resolved only as far as it reaches the next
   // segment (its picks' suppression past ep), since nothing else of it is observable there: the

@@ -188,23 +188,32 @@ def _codes(paths):
     return corner, surf
 
 
-def _batch_bytes(cfg, scans):
-    """Poses + stats bytes of a default batch launch of `scans` against the config's map."""
+def _batch_bytes(cfg, scans, paths=False):
+    """Poses + stats bytes of a default batch launch of `scans` against the config's map; with
+    `paths` the path record's words behind them."""
     with api.Context(synth.config_params(cfg, max_batch=len(scans))) as ctx:
         ctx.set_map(*synth.config_map(cfg))
+        if paths:
+            ctx.feature_paths()  # arm the record
         p, s = ctx.process_batch(scans, np.zeros((len(scans), 6), np.float32))
-    return p.tobytes() + s.tobytes()
+        rec = ctx.feature_paths().tobytes() if paths else b""
+    return p.tobytes() + s.tobytes() + rec
 
 
-def _stream_bytes(scans):
-    """fbr_process_scan over `scans`, then fbr_extract_features on the last projection."""
+def _stream_bytes(scans, paths=False):
+    """fbr_process_scan over `scans`, then fbr_extract_features on the last projection; with `paths`
+    each scan's path record behind its results."""
     out = b""
     with api.Context(synth.config_params("C1")) as ctx:
         ctx.set_map(*synth.config_map("C1"))
+        if paths:
+            ctx.feature_paths()  # arm the record
         pose = np.zeros(6, np.float32)
         for k, pts in enumerate(scans):
             pose, st = ctx.process_scan(pts, 0.2 * k, pose)
             out += pose.tobytes() + np.array([st[f] for f in sorted(st)], np.float64).tobytes()
+            if paths:
+                out += ctx.feature_paths().tobytes()
         f = ctx.extract_features(len(ctx.project(scans[-1])["col_ind"]))
         out += f["label"].tobytes() + f["corner"].tobytes() + f["surf"].tobytes()
     return out
@@ -275,3 +284,28 @@ def test_compact_walks_equal_member_indexed_walks_stream():
     over a synthetic scan and two crafted ones: every result byte equals FBR_FEAT_COMPACT=0's."""
     scans = [synth.scan(synth.job(3)[0], H1, W1, seed=3)] + _scans()[:2]
     assert _in_child("T._stream_bytes(sc)", scans, {"FBR_FEAT_COMPACT": "0"}) == _stream_bytes(scans)
+
+
+@pytest.fixture(scope="module")
+def instance_cases():
+    """[(name, child expression, scans, this process's bytes)]: the crafted C1 batch, two C3 jobs
+    (2048 columns) and the single-scan stream of the stream test, each with its path record,
+    computed once with the default wave count."""
+    crafted = _scans()
+    c3 = [j[0] for j in synth.make_jobs("C3", 2, base_seed=871)]
+    stream = [synth.scan(synth.job(3)[0], H1, W1, seed=3)] + crafted[:2]
+    return [("batch C1", "T._batch_bytes('C1', sc, True)", crafted, _batch_bytes("C1", crafted, True)),
+            ("batch C3", "T._batch_bytes('C3', sc, True)", c3, _batch_bytes("C3", c3, True)),
+            ("stream C1", "T._stream_bytes(sc, True)", stream, _stream_bytes(stream, True))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["1", "2"])
+def test_every_wave_count_instance_gives_the_default_bytes(instance_cases, waves):
+    """k_features' template instances: these launches are small, so by default they all run with four
+    waves per ring (<6,4,4>).  FBR_FEAT_WAVES=1 runs <5,4,1> on 1800 columns and <6,4,1> on 2048,
+    FBR_FEAT_WAVES=2 runs <6,4,2> on both.  Every result byte and every path-record word of the
+    crafted batch, the C3 jobs and the stream equals this process's."""
+    for name, expr, scans, want in instance_cases:
+        got = _in_child(expr, scans, {"FBR_FEAT_WAVES": waves})
+        assert len(got) == len(want) and got == want, (name, waves)

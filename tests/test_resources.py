@@ -3,7 +3,8 @@
 CPU: tests/native/own_check.cpp instantiates the header over a counting malloc / free policy and
 checks the handle semantics under AddressSanitizer and UBSan, as a stand-alone program;
 tests/native/pace_check.cpp does the same for csrc/fbr_pace.h, the host loops paced by words in the
-host-mapped blocks (HostWord) these handles own.
+host-mapped blocks (HostWord) these handles own, and tests/native/feat_layout_check.cpp for
+csrc/fbr_feat_layout.h, the sizes of the LDS and scratch blocks k_features is launched with.
 
 GPU: fbr_diag_live_resources counts the device blocks, pinned blocks, streams and events the
 process's contexts and communicators hold.  Each test runs in a child process (no other context
@@ -53,6 +54,23 @@ def test_host_pacing_under_sanitizers():
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "pace_check: ok" in r.stdout
+
+
+def test_features_layout_under_sanitizers():
+    """csrc/fbr_feat_layout.h alone, for every Horizon_SCAN 1 .. 4096 and 1, 2 or 4 waves per ring:
+    the capacities, the LDS total and the scratch-slot total equal the formulas the kernel unit and
+    feat_caps held before the header (written out in the program); every 64-bit array sits on 8
+    bytes, region B and the slot's curvature on 16; every region-B tenant ends inside region B; and
+    the tenants the header's table declares live together do not overlap."""
+    out_dir = os.path.join(NATIVE, "build")
+    os.makedirs(out_dir, exist_ok=True)
+    exe = os.path.join(out_dir, "feat_layout_check")
+    subprocess.check_call(["g++", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", "-I", CSRC, "-o", exe,
+                           os.path.join(NATIVE, "feat_layout_check.cpp")])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "feat_layout_check: ok" in r.stdout
 
 
 def run_child(script, env_set=None):
