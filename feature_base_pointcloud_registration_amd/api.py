@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
     "fbr_pg_params_default", "fbr_pg_reset", "fbr_pg_add_prior", "fbr_pg_add_between", "fbr_pg_add_between_poses",
     "fbr_pg_add_gps", "fbr_pg_add_loop", "fbr_pg_factor_count", "fbr_pg_optimize", "fbr_pg_poses", "fbr_pg_apply",
+    "fbr_pg_loop_weights",
     "fbr_pg_marginal_params_default", "fbr_pg_marginals", "fbr_pg_gps_gate",
     "fbr_gmap_params_default", "fbr_global_map_build", "fbr_global_map_get", "fbr_global_map_install",
     "fbr_global_map_save", "fbr_pcd_write_poses_ascii", "fbr_selftest_voxel_wide",
@@ -154,6 +155,7 @@ def lib():
             "fbr_pg_optimize": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_pg_poses": (ctypes.c_int, [_VP, _VP, _I64, _VP]),
             "fbr_pg_apply": (ctypes.c_int, [_VP]),
+            "fbr_pg_loop_weights": (ctypes.c_int, [_VP, _VP, _VP, _VP, _I64, _VP]),
             "fbr_pg_marginal_params_default": (None, [_VP]),
             "fbr_pg_marginals": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP]),
             "fbr_pg_gps_gate": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP]),
@@ -737,6 +739,19 @@ class Context:
         _check(lib().fbr_pg_optimize(self._h, ctypes.byref(p), ctypes.byref(r)), "fbr_pg_optimize")
         poses = self.pg_poses() if r.n_nodes > 0 else np.zeros((0, 6), np.float64)
         return poses, (r if raw else r.as_dict())
+
+    def pg_loop_weights(self):
+        """Every loop factor in add order at the last optimise's poses: (index in the factor list int32
+        [K], chi2 = |r|^2 of the whitened residual float64 [K], robust weight float64 [K]; the weights
+        are 1 without a robust option)."""
+        n = _I64()
+        rc = lib().fbr_pg_loop_weights(self._h, None, None, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):  # FBR_ERR_CAPACITY: the count is in n
+            _check(rc, "fbr_pg_loop_weights")
+        k = max(n.value, 1)
+        idx, chi2, w = np.zeros(k, np.int32), np.zeros(k, np.float64), np.zeros(k, np.float64)
+        _check(lib().fbr_pg_loop_weights(self._h, ptr(idx), ptr(chi2), ptr(w), k, ctypes.byref(n)), "fbr_pg_loop_weights")
+        return idx[:n.value], chi2[:n.value], w[:n.value]
 
     def pg_apply(self):
         """correctPoses: the optimised poses, rounded to float, become the key poses."""

@@ -493,6 +493,13 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   GrowDev<double> d_pg_marg;       // every double array of a marginals call (fbr_pg.hip pg_marginals_run)
   GrowDev<int32_t> d_pg_loops;     // the loop factors' indices, in factor order
   GrowDev<int64_t> d_pg_nodes;     // the requested nodes, then the distinct ones in ascending order
+  // robust loop factors and the direct solve (fbr_pg_params.robust / solver; kernels: k_posegraph.hip's
+  // k_pg_robust, k_pg_direct.hip over k_pg_marginals.hip's launchers)
+  int32_t pg_result_robust = 0;    // the last optimise's robust option: the marginals use it too
+  double pg_result_scale = 0.0;
+  std::vector<int32_t> pg_loop_index;        // fbr_pg_loop_weights: the loop factors' indices in add order,
+  std::vector<double> pg_loop_chi2, pg_loop_w;  // their |r|^2 and weight at the result poses
+  GrowDev<double> d_pg_direct;     // W, the chunk's right-hand sides per level, C and z of a direct solve
 
   // ---- global map (fbr_gmap.hip) ----
   // The clouds of the last fbr_global_map_build, until the next build, fbr_keyframes_reset or

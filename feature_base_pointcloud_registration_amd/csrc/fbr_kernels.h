@@ -573,8 +573,15 @@ struct PgArgs {
   unsigned long long* flag;  // host-mapped: (generation << 32) | iterations << 1 | stopped
   int nlev;
   PgLevel lev[kPgMaxLevels];
+  int robust;          // kPgRobust*: other than none, k_pg_robust follows k_pg_linearize
+  double robust_scale;
+  double *chi2, *wt;   // [nf] a factor's |r|^2 and robust weight (written by k_pg_robust only)
+  const int32_t* loops;  // [nloops] the loop factors' indices, in factor order
+  int64_t nloops;
+  double* report;      // [2][nloops] the loop factors' |r|^2, then their weights (k_pg_loop_report)
 };
-// residuals (jac: and Jacobians) of the factors at poses X [n][12]; the cost into st->cost[slot]
+// residuals (jac: and Jacobians) of the factors at poses X [n][12], the loop factors re-weighted when
+// a.robust asks for it; the cost into st->cost[slot]
 void launch_pg_linearize(hipStream_t s, const PgArgs& a, const double* X, int jac, int slot);
 void launch_pg_assemble(hipStream_t s, const PgArgs& a);
 // level 0's D = D0 + lambda diag(hd), then the cyclic-reduction factor of every level
@@ -583,6 +590,10 @@ void launch_pg_factor(hipStream_t s, const PgArgs& a, double lambda);
 void launch_pg_pcg_init(hipStream_t s, const PgArgs& a, unsigned long long gen);
 void launch_pg_pcg_iter(hipStream_t s, const PgArgs& a, int it, int max_it, double tol2, unsigned long long gen);
 void launch_pg_retract(hipStream_t s, const PgArgs& a, const double* X, double* Xt);
+// the loop factors' |r|^2 and weights of the last evaluation into a.report (fbr_pg_loop_weights)
+void launch_pg_loop_report(hipStream_t s, const PgArgs& a);
+// the direct solve's first step: level 0's x = y = T^-1 (-g) with the factor launch_pg_factor left
+void launch_pg_direct_y(hipStream_t s, const PgArgs& a);
 
 // ---- pose-graph marginal covariances (k_pg_marginals.hip; the arithmetic is fbr_pg.h's) ----
 struct PgMarg {
@@ -609,5 +620,23 @@ void launch_pg_marg_chol(hipStream_t s, const PgMarg& a);
 // (null: every node) into out [n_out][36]
 void launch_pg_marg_cov(hipStream_t s, const PgMarg& a, const int64_t* uniq, int64_t n_uniq, const int64_t* nodes,
                         int64_t n_out, double* out);
+
+// ---- the pose graph's direct solve (k_pg_direct.hip; the arithmetic is fbr_pg.h's) ----
+// After launch_pg_factor, launch_pg_direct_y and, on a PgMarg over the damped levels,
+// launch_pg_marg_solve, launch_pg_marg_c and launch_pg_marg_chol.
+struct PgDirect {
+  int64_t n, M;                // nodes, M = 6 K
+  const PgFactor* fac;
+  const double* lin;
+  const int32_t* loops;        // [K] the loop factors' indices
+  const double* W;             // [M][6][n] T^-1 U^T
+  const double* C;             // [M][M] the Cholesky factor of I + U W
+  const double* y;             // [6][n] T^-1 (-g)
+  double* z;                   // [M] U y, then s
+  double* x;                   // [6][n] the step (PgArgs::x)
+};
+void launch_pg_direct_z(hipStream_t s, const PgDirect& d);      // z = U y
+void launch_pg_direct_subst(hipStream_t s, const PgDirect& d);  // Lc Lc^T s = z, in place
+void launch_pg_direct_delta(hipStream_t s, const PgDirect& d);  // x = y - W s (M = 0: x = y)
 
 }  // namespace fbr

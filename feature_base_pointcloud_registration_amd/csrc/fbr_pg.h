@@ -1,7 +1,8 @@
 // fbr_pg.h — the pose-graph arithmetic of include/fbr.h ("pose graph"), host and device, all in
 // double: Exp / Log / Jr^-1 of SO(3), the residual and Jacobians of a factor, the 6x6 Cholesky, one
-// level step of the block cyclic reduction with its index arithmetic, the Euler conversion, and the
-// per-node steps of the marginal covariances (k_pg_marginals.hip; on the CPU fbr_pg_host.h).
+// level step of the block cyclic reduction with its index arithmetic, the Euler conversion, the
+// per-node steps of the marginal covariances (k_pg_marginals.hip; on the CPU fbr_pg_host.h), the
+// robust loop factors' rho and weight, and the per-entry steps of the direct solve (k_pg_direct.hip).
 // k_posegraph.hip compiles these functions for the device and tests/native/pg_probe.cpp for the CPU,
 // so the tests check the kernels' arithmetic without a GPU.  The contract is the project's own
 // restatement of a pose-graph optimiser in GTSAM 4.0's default Pose3 chart; it is pinned by the
@@ -861,6 +862,102 @@ PG_HD void pg_marg_final(const double* P, const double* Y, int64_t M, int64_t n,
       out[6 * r + c] = v;
       out[6 * c + r] = v;
     }
+}
+
+// ---- robust loop factors (include/fbr.h "robust loop factors") ----
+enum { kPgRobustNone = 0, kPgRobustHuber = 1, kPgRobustCauchy = 2 };
+
+// rho and the weight w = 2 rho'(s) of a factor whose whitened residual has s = |r|^2; k is the
+// scale, in units of e = sqrt(s).  kPgRobustNone: rho = s / 2, w = 1.
+PG_HD void pg_robust(int kind, double k, double s, double* rho, double* w) {
+  if (kind == kPgRobustHuber) {
+    const double e = sqrt(s);
+    if (e <= k) {
+      *rho = 0.5 * s;
+      *w = 1.0;
+    } else {
+      *rho = k * (e - 0.5 * k);
+      *w = k / e;
+    }
+  } else if (kind == kPgRobustCauchy) {
+    const double q = s / (k * k);
+    *rho = (0.5 * (k * k)) * log1p(q);
+    *w = 1.0 / (1.0 + q);
+  } else {
+    *rho = 0.5 * s;
+    *w = 1.0;
+  }
+}
+
+// Factor f after its evaluation (fcost[f] = s / 2, and with jac its kPgLin doubles of lin): chi2[f]
+// = s and wt[f] = w always; a loop factor's fcost becomes rho and, with jac, its r, J_i and J_j
+// are scaled by sqrt(w) (GTSAM's noiseModel::Robust whitens this way).  Every other factor keeps
+// rho = s / 2 and w = 1.
+PG_HD void pg_robust_factor(const PgFactor* fac, int64_t f, int kind, double k, bool jac, double* lin, double* fcost,
+                            double* chi2, double* wt) {
+  const double s = 2.0 * fcost[f];
+  double rho = fcost[f], w = 1.0;
+  if (fac[f].loop) pg_robust(kind, k, s, &rho, &w);
+  chi2[f] = s;
+  wt[f] = w;
+  if (!fac[f].loop) return;
+  fcost[f] = rho;
+  if (!jac) return;
+  const double sw = sqrt(w);
+  double* o = lin + f * kPgLin;
+  for (int e = 0; e < kPgLin; ++e) o[e] = o[e] * sw;
+}
+
+// ---- the direct solve of a damped step (include/fbr.h "direct solve") ----
+// H = T + U^T U with T the damped block-tridiagonal part, factored by the cyclic reduction above,
+// and U the loop factors' whitened Jacobians, as in the marginals:
+//   y = T^-1 (-g),  W = T^-1 U^T,  C = I + U W = Lc Lc^T  (the marginals' steps, on the damped T)
+//   z = U y (pg_direct_z_entry),  Lc Lc^T s = z (pg_subst_*),  delta = y - W s (pg_direct_delta_entry).
+
+// z[row] = U[row] . y, row = 6 f + r: J_i's row r against node i's six entries of y [6][n], then
+// J_j's against node j's.
+PG_HD double pg_direct_z_entry(const PgFactor* fac, const double* lin, const int32_t* loops, const double* y, int64_t n,
+                               int64_t row) {
+  const int32_t fk = loops[row / 6];
+  const int r = (int)(row % 6);
+  const double* Ji = lin + (int64_t)fk * kPgLin + 6 + 6 * r;
+  const double* Jj = Ji + 36;
+  const int64_t i = fac[fk].i, j = fac[fk].j;
+  double s = 0.0;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) s = s + Ji[e] * y[e * n + i];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) s = s + Jj[e] * y[e * n + j];
+  return s;
+}
+
+// The two operations of a substitution that sweeps the columns: finish entry k, then take its term
+// out of every entry that still waits for it.
+PG_HD double pg_subst_pivot(double v, double d) { return v / d; }
+PG_HD double pg_subst_sub(double v, double l, double s) { return v - l * s; }
+
+// Lc Lc^T s = z in place on z [M] (Lc row-major, lower), column by column: forwards k = 0 .. M-1
+// with Lc's column k on the rows below, backwards k = M-1 .. 0 with Lc's row k on the rows above.
+// An entry takes its terms in the order in which they become known: ascending k forwards,
+// descending k backwards.  k_pg_direct_subst spreads the inner loops over a workgroup; the
+// operations per entry and their order are these.
+PG_HD void pg_dense_subst(const double* Lc, int64_t M, double* z) {
+  for (int64_t k = 0; k < M; ++k) {
+    z[k] = pg_subst_pivot(z[k], Lc[k * M + k]);
+    for (int64_t r = k + 1; r < M; ++r) z[r] = pg_subst_sub(z[r], Lc[r * M + k], z[k]);
+  }
+  for (int64_t k = M - 1; k >= 0; --k) {
+    z[k] = pg_subst_pivot(z[k], Lc[k * M + k]);
+    for (int64_t r = 0; r < k; ++r) z[r] = pg_subst_sub(z[r], Lc[k * M + r], z[k]);
+  }
+}
+
+// delta[t] = y[t] - sum_col W[col][t] s[col], t = e n + m an entry of the [6][n] vectors, the sum
+// over the columns in ascending order (M = 0: delta = y).
+PG_HD double pg_direct_delta_entry(const double* y, const double* W, const double* s, int64_t M, int64_t n, int64_t t) {
+  double acc = 0.0;
+  for (int64_t col = 0; col < M; ++col) acc = acc + W[col * 6 * n + t] * s[col];
+  return M > 0 ? y[t] - acc : y[t];
 }
 
 }  // namespace fbr

@@ -37,7 +37,7 @@ struct PgPlan {
   double *X, *Xt;
 };
 
-int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
+int pg_prepare(fbr_ctx* c, int64_t n, int robust, double robust_scale, PgPlan* pl) {
   const std::vector<PgFactor>& F = c->pg_factors;
   const int64_t nf = (int64_t)F.size();
   // adjacency in factor order: every factor, and the loop factors alone
@@ -57,12 +57,13 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
     off[m + 1] += off[m];
     loff[m + 1] += loff[m];
   }
-  const int64_t na = off[n], nla = loff[n];
-  adj.resize((size_t)(2 * (n + 1) + na + nla));
+  const int64_t na = off[n], nla = loff[n], nloops = nla / 2;
+  adj.resize((size_t)(2 * (n + 1) + na + nla + nloops));
   off = adj.data();
   loff = adj.data() + n + 1;
   int32_t* ent = adj.data() + 2 * (n + 1);
   int32_t* lent = ent + na;
+  int32_t* loops = lent + nla;  // the loop factors' indices
   std::vector<int32_t> cur(off, off + n), lcur(loff, loff + n);
   for (int64_t k = 0; k < nf; ++k) {
     const PgFactor& f = F[k];
@@ -71,13 +72,14 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
     if (f.loop) {
       lent[lcur[f.i]++] = (int32_t)(2 * k);
       lent[lcur[f.j]++] = (int32_t)(2 * k + 1);
+      *loops++ = (int32_t)k;
     }
   }
   int64_t tot = 0;
   const int nlev = pg_cr_levels(n, &tot);
   if (nlev > kPgMaxLevels || nf >= ((int64_t)1 << 30) || n >= ((int64_t)1 << 30)) return FBR_ERR_CAPACITY;
   const int64_t nbmax = (std::max(n, nf) + 255) / 256;
-  const int64_t words = 24 * n + (kPgLin + 1) * nf + 36 * n + 12 * n + 24 * n + nbmax + tot * (36 * 5 + 12);
+  const int64_t words = 24 * n + (kPgLin + 1) * nf + 36 * n + 12 * n + 24 * n + nbmax + tot * (36 * 5 + 12) + 2 * nf + 2 * nloops;
   int rc = grow(c->d_pg_work, words, 0, c->stream);
   if (!rc) rc = grow(c->d_pg_adj, (int64_t)adj.size(), 0, c->stream);
   if (!rc) rc = grow(c->d_pg_fac, std::max<int64_t>(nf, 1), 0, c->stream);
@@ -130,6 +132,13 @@ int pg_prepare(fbr_ctx* c, int64_t n, PgPlan* pl) {
     lv.b = take(6 * ln);
     lv.x = take(6 * ln);
   }
+  a.robust = robust;
+  a.robust_scale = robust_scale;
+  a.chi2 = take(nf);
+  a.wt = take(nf);
+  a.loops = a.ladj + nla;
+  a.nloops = nloops;
+  a.report = take(2 * nloops);
   return FBR_OK;
 }
 
@@ -154,6 +163,87 @@ int pg_read_state(fbr_ctx* c, PgState* st) {
   return FBR_OK;
 }
 
+constexpr int kPgMargChunk = 48;                             // fbr_pg_marginal_params.rhs_chunk's default
+constexpr int64_t kPgMargMaxWork = (int64_t)2 << 30;         // ... and max_work_bytes' (2 GiB)
+constexpr int64_t kPgDirectMaxWorkMb = 2048;                 // fbr_pg_params.max_work_mb's default
+
+// The direct solve (fbr_pg_params.solver = FBR_PG_SOLVER_DIRECT): W and C as the marginals build
+// them, here over the optimise's own damped levels, and k_pg_direct.hip's three steps.
+struct PgDirectPlan {
+  PgMarg m;
+  PgDirect d;
+  int64_t chunk;
+};
+
+// The doubles of its work space: W, the chunk's b of every level and x of the levels after the
+// first, C and z (in double: the products overflow an int64 long after the bound).  None without loops.
+double pg_direct_words(int64_t n, int64_t K, int64_t* chunk) {
+  const int64_t M = 6 * K;
+  int64_t tot = 0;
+  (void)pg_cr_levels(n, &tot);
+  *chunk = std::min<int64_t>(kPgMargChunk, std::max<int64_t>(M, 1));
+  if (M == 0) return 0.0;
+  return 6.0 * (double)M * (double)n + 6.0 * (double)*chunk * (double)(2 * tot - n) + (double)M * (double)M + (double)M;
+}
+
+int pg_direct_prepare(fbr_ctx* c, const PgArgs& a, PgDirectPlan* dp) {
+  const int64_t n = a.n, K = a.nloops, M = 6 * K;
+  const int64_t words = (int64_t)pg_direct_words(n, K, &dp->chunk);
+  PgMarg& m = dp->m;
+  PgDirect& d = dp->d;
+  m = PgMarg{};
+  d = PgDirect{};
+  d.n = n;
+  d.M = M;
+  d.fac = a.fac;
+  d.lin = a.lin;
+  d.y = a.lev[0].x;
+  d.x = a.x;
+  if (M == 0) return FBR_OK;  // the step is y: no W, no C
+  const int rc = grow(c->d_pg_direct, words, 0, c->stream);
+  if (rc) return rc;
+  m.n = n;
+  m.K = K;
+  m.M = M;
+  m.nlev = a.nlev;
+  m.fac = a.fac;
+  m.lin = a.lin;
+  m.loops = a.loops;
+  m.st = a.st;
+  double* w = c->d_pg_direct;
+  auto take = [&w](int64_t count) {
+    double* p = w;
+    w += count;
+    return p;
+  };
+  for (int l = 0; l < a.nlev; ++l) {
+    m.lev[l] = a.lev[l];
+    m.lev[l].b = take(6 * dp->chunk * a.lev[l].n);
+    m.lev[l].x = l ? take(6 * dp->chunk * a.lev[l].n) : nullptr;  // level 0's x is the chunk's part of W
+  }
+  m.W = take(6 * M * n);
+  m.C = take(M * M);
+  d.z = take(M);
+  d.loops = m.loops;
+  d.W = m.W;
+  d.C = m.C;
+  return FBR_OK;
+}
+
+// One damped solve after launch_pg_factor, into a.x; nothing waits.  A bad pivot of C sets
+// PgState::numerical as one of T does.
+void pg_direct(fbr_ctx* c, const PgArgs& a, const PgDirectPlan& dp) {
+  const PgMarg& m = dp.m;
+  TIMED(c, "pg_direct_y", launch_pg_direct_y(c->stream, a));
+  for (int64_t c0 = 0; c0 < m.M; c0 += dp.chunk)
+    TIMED(c, "pg_marg_solve", launch_pg_marg_solve(c->stream, m, c0, std::min(dp.chunk, m.M - c0)));
+  TIMED(c, "pg_marg_c", launch_pg_marg_c(c->stream, m));
+  TIMED(c, "pg_marg_chol", launch_pg_marg_chol(c->stream, m));
+  TIMED(c, "pg_direct_z", launch_pg_direct_z(c->stream, dp.d));
+  TIMED(c, "pg_direct_subst", launch_pg_direct_subst(c->stream, dp.d));
+  TIMED(c, "pg_direct_delta", launch_pg_direct_delta(c->stream, dp.d));
+}
+
 int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
   const int64_t n = (int64_t)c->kf_poses.size();
   out->n_nodes = (int32_t)n;
@@ -165,10 +255,18 @@ int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
     out->status = FBR_PG_EMPTY;
     return FBR_OK;
   }
+  const bool direct = P.solver == FBR_PG_SOLVER_DIRECT;
+  if (direct) {  // before anything is allocated
+    int64_t chunk = 0;
+    const double mb = (double)(P.max_work_mb > 0 ? (int64_t)P.max_work_mb : kPgDirectMaxWorkMb);
+    if (8.0 * pg_direct_words(n, out->n_loop_factors, &chunk) > mb * 1048576.0) return FBR_ERR_CAPACITY;
+  }
   PgPlan pl;
-  int rc = pg_prepare(c, n, &pl);
+  int rc = pg_prepare(c, n, P.robust, (double)P.robust_scale, &pl);
   if (rc) return rc;
   const PgArgs& a = pl.a;
+  PgDirectPlan dp;
+  if (direct && (rc = pg_direct_prepare(c, a, &dp))) return rc;
   std::vector<double> X0((size_t)(12 * n)), init((size_t)(6 * n));
   for (int64_t i = 0; i < n; ++i) {
     keypose_euler(c->kf_poses[i], &init[6 * i]);
@@ -189,7 +287,8 @@ int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
   else if (P.max_iterations <= 0) status = FBR_PG_ITERATIONS;
   while (status < 0) {
     TIMED(c, "pg_factor", launch_pg_factor(c->stream, a, lambda));
-    pg_pcg(c, a, P);
+    if (direct) pg_direct(c, a, dp);
+    else pg_pcg(c, a, P);
     TIMED(c, "pg_retract", launch_pg_retract(c->stream, a, X, Xt));
     TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, Xt, 0, 1));
     rc = pg_read_state(c, &st);
@@ -220,8 +319,22 @@ int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
   }
   out->status = status;
   out->lambda = lambda;
+  // fbr_pg_loop_weights: the per-factor values of the evaluation at the result poses.  That is the
+  // last one enqueued unless it was a rejected trial's; then the result poses are evaluated again.
+  const int64_t nf = a.nf;
+  if (status == FBR_PG_NUMERICAL || status == FBR_PG_STALLED) {
+    if (status == FBR_PG_NUMERICAL) CK(hipMemcpyAsync(X, X0.data(), sizeof(double) * 12 * n, hipMemcpyHostToDevice, c->stream));
+    TIMED(c, "pg_linearize", launch_pg_linearize(c->stream, a, X, 0, 1));
+  }
+  const int64_t K = a.nloops;
+  std::vector<double> report((size_t)(2 * K));
+  if (K) {  // (a graph without loops launches and copies nothing more)
+    TIMED(c, "pg_loop_report", launch_pg_loop_report(c->stream, a));
+    CK(hipMemcpyAsync(report.data(), a.report, sizeof(double) * 2 * K, hipMemcpyDeviceToHost, c->stream));
+  }
   c->pg_result.assign((size_t)(6 * n), 0.0);
   if (status == FBR_PG_NUMERICAL) {  // the optimised poses are the initial ones
+    CK(fbr_sync(c->stream));
     c->pg_result = init;
   } else {
     out->cost_final = cost;
@@ -240,13 +353,17 @@ int pg_run(fbr_ctx* c, const fbr_pg_params& P, fbr_pg_result* out) {
           std::max(out->max_rotation_change, std::sqrt((phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2]));
     }
   }
+  c->pg_loop_index.clear();
+  for (int64_t k = 0; k < nf; ++k)
+    if (c->pg_factors[k].loop) c->pg_loop_index.push_back((int32_t)k);
+  c->pg_loop_chi2.assign(report.begin(), report.begin() + K);
+  c->pg_loop_w.assign(report.begin() + K, report.end());
+  c->pg_result_robust = P.robust;
+  c->pg_result_scale = (double)P.robust_scale;
   c->pg_result_n = n;
   c->pg_result_nf = (int64_t)c->pg_factors.size();
   return FBR_OK;
 }
-
-constexpr int kPgMargChunk = 48;                             // fbr_pg_marginal_params.rhs_chunk's default
-constexpr int64_t kPgMargMaxWork = (int64_t)2 << 30;         // ... and max_work_bytes' (2 GiB)
 
 // Sigma_ii of the requested nodes at the last optimise's poses (include/fbr.h "marginal
 // covariances").  Everything is enqueued without waiting; the host reads the result and the status
@@ -286,7 +403,7 @@ int pg_marginals_run(fbr_ctx* c, const fbr_pg_marginal_params& P, const int64_t*
   const int64_t words = 72 * tot + 6 * std::max<int64_t>(M, 1) * n + 6 * chunk * (2 * tot - n) + M * M + 36 * n_out;
   out->work_bytes = 8 * words;
   PgPlan pl;
-  int rc = pg_prepare(c, n, &pl);
+  int rc = pg_prepare(c, n, c->pg_result_robust, c->pg_result_scale, &pl);
   if (rc) return rc;
   const PgArgs& a = pl.a;
   // the distinct requested nodes in ascending order: Y is computed in place, once per node
@@ -361,7 +478,11 @@ int pg_marginals_run(fbr_ctx* c, const fbr_pg_marginal_params& P, const int64_t*
 bool pg_params_ok(const fbr_pg_params* p) {
   return p && p->max_pcg_iterations >= 1 && p->rel_cost_tol >= 0.0 && p->abs_cost_tol >= 0.0 && p->pcg_rel_tol >= 0.0 &&
          p->lambda_init > 0.0 && p->lambda_init < INFINITY && p->lambda_factor > 1.0 && p->lambda_factor < INFINITY &&
-         p->lambda_max > 0.0;
+         p->lambda_max > 0.0 && (p->solver == FBR_PG_SOLVER_PCG || p->solver == FBR_PG_SOLVER_DIRECT) &&
+         (p->robust == FBR_PG_ROBUST_NONE ||
+          ((p->robust == FBR_PG_ROBUST_HUBER || p->robust == FBR_PG_ROBUST_CAUCHY) && p->robust_scale > 0.0f &&
+           p->robust_scale < INFINITY)) &&
+         p->max_work_mb >= 0;
 }
 
 }  // namespace
@@ -473,6 +594,20 @@ int fbr_pg_poses(fbr_ctx* c, double* poses_out, int64_t cap, int64_t* n) {
   *n = c->pg_result_n;
   if (cap < c->pg_result_n) return FBR_ERR_CAPACITY;
   std::memcpy(poses_out, c->pg_result.data(), sizeof(double) * 6 * c->pg_result_n);
+  return FBR_OK;
+}
+
+int fbr_pg_loop_weights(fbr_ctx* c, int32_t* factor_index_out, double* chi2_out, double* weight_out, int64_t cap, int64_t* n) {
+  if (!c || !n || cap < 0 || (cap && (!factor_index_out || !chi2_out || !weight_out))) return FBR_ERR_INVALID_ARG;
+  if (c->pg_result_n < 0) return FBR_ERR_STATE;
+  const int64_t K = (int64_t)c->pg_loop_index.size();
+  *n = K;
+  if (cap < K) return FBR_ERR_CAPACITY;
+  if (K) {
+    std::memcpy(factor_index_out, c->pg_loop_index.data(), sizeof(int32_t) * K);
+    std::memcpy(chi2_out, c->pg_loop_chi2.data(), sizeof(double) * K);
+    std::memcpy(weight_out, c->pg_loop_w.data(), sizeof(double) * K);
+  }
   return FBR_OK;
 }
 

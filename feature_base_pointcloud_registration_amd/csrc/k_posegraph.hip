@@ -4,6 +4,9 @@
 // fbr_pg.h's, shared with the CPU probe.
 //
 // k_pg_linearize: one thread per factor: whitened residual, Jacobian blocks, 1/2 |r|^2.
+// k_pg_robust:    only with a robust option, after k_pg_linearize: one thread per factor turns a loop
+//   factor's cost into rho and scales its linearisation by sqrt(w); k_pg_loop_report gathers the loop
+//   factors' |r|^2 and weights at the end of an optimise (fbr_pg_loop_weights).
 // k_pg_assemble:  one thread per node gathers its factors (host-built adjacency, factor order) into
 //   T's diagonal and sub-diagonal blocks, g = J^T r and diag(H).  No atomics.
 // k_pg_damp, k_pg_cr_elim, k_pg_cr_update: level 0's damped diagonal, then per level the Cholesky of
@@ -68,6 +71,27 @@ k_pg_linearize(PgArgs a, const double* __restrict__ X, int jac) {
     o[6 + e] = Ji[e];
     o[42 + e] = Jj[e];
   }
+}
+
+// After k_pg_linearize when a robust cost is asked for: one thread per factor; a loop factor's cost
+// becomes rho and, with jac, its linearisation is scaled by sqrt(w) (pg_robust_factor).
+__global__ void __launch_bounds__(kPgThreads)
+k_pg_robust(PgArgs a, int jac) {
+  const int64_t k = (int64_t)blockIdx.x * kPgThreads + threadIdx.x;
+  if (k >= a.nf) return;
+  pg_robust_factor(a.fac, k, a.robust, a.robust_scale, jac != 0, a.lin, a.fcost, a.chi2, a.wt);
+}
+
+// The loop factors' |r|^2 and weight of the last evaluation, gathered for one small copy to the host:
+// k_pg_robust's values, or 2 fcost and 1 without a robust option.
+__global__ void __launch_bounds__(kPgVec)
+k_pg_loop_report(PgArgs a) {
+  const int64_t l = (int64_t)blockIdx.x * kPgVec + threadIdx.x;
+  if (l >= a.nloops) return;
+  const int32_t f = a.loops[l];
+  const bool robust = a.robust != kPgRobustNone;
+  a.report[l] = robust ? a.chi2[f] : 2.0 * a.fcost[f];
+  a.report[a.nloops + l] = robust ? a.wt[f] : 1.0;
 }
 
 // partial[b] = the sum of v[b * 256 ..) in tree order
@@ -296,6 +320,7 @@ static inline int pg_tail_level(const PgArgs& a) {
 void launch_pg_linearize(hipStream_t s, const PgArgs& a, const double* X, int jac, int slot) {
   if (a.nf <= 0) return;
   fbr_launch(k_pg_linearize, dim3(pg_blocks(a.nf, kPgThreads)), dim3(kPgThreads), 0, s, a, X, jac);
+  if (a.robust != kPgRobustNone) fbr_launch(k_pg_robust, dim3(pg_blocks(a.nf, kPgThreads)), dim3(kPgThreads), 0, s, a, jac);
   const unsigned nb = pg_blocks(a.nf, kPgVec);
   fbr_launch(k_pg_sum_partial, dim3(nb), dim3(kPgVec), 0, s, (const double*)a.fcost, a.nf, a.partial);
   fbr_launch(k_pg_cost_final, dim3(1), dim3(1), 0, s, a, (int)nb, slot);
@@ -335,6 +360,17 @@ void launch_pg_pcg_init(hipStream_t s, const PgArgs& a, unsigned long long gen) 
   fbr_launch(k_pg_dot, dim3(nb), dim3(kPgVec), 0, s, a, (const double*)a.r, (const double*)a.lev[0].x);
   fbr_launch(k_pg_decide, dim3(1), dim3(1), 0, s, a, (int)nb, 1, 0, 0, 0.0, gen);
   fbr_launch(k_pg_pupdate, dim3(nv), dim3(kPgVec), 0, s, a);
+}
+
+void launch_pg_loop_report(hipStream_t s, const PgArgs& a) {
+  if (a.nloops <= 0) return;
+  fbr_launch(k_pg_loop_report, dim3(pg_blocks(a.nloops, kPgVec)), dim3(kPgVec), 0, s, a);
+}
+
+// k_pg_pcg_start's right-hand side -g (and a cleared stop word: the solve's kernels run), one solve
+void launch_pg_direct_y(hipStream_t s, const PgArgs& a) {
+  fbr_launch(k_pg_pcg_start, dim3(pg_blocks(6 * a.n, kPgVec)), dim3(kPgVec), 0, s, a);
+  pg_solve(s, a);
 }
 
 void launch_pg_pcg_iter(hipStream_t s, const PgArgs& a, int it, int max_it, double tol2, unsigned long long gen) {

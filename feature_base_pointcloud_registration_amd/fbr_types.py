@@ -138,13 +138,18 @@ def sc_params(**kw):
 
 # pose graph (include/fbr.h "pose graph")
 FBR_PG_CONVERGED, FBR_PG_ITERATIONS, FBR_PG_STALLED, FBR_PG_NUMERICAL, FBR_PG_EMPTY = range(5)
+FBR_PG_SOLVER_PCG, FBR_PG_SOLVER_DIRECT = range(2)
+FBR_PG_ROBUST_NONE, FBR_PG_ROBUST_HUBER, FBR_PG_ROBUST_CAUCHY = range(3)
+PG_SOLVERS = {"pcg": FBR_PG_SOLVER_PCG, "direct": FBR_PG_SOLVER_DIRECT}
+PG_ROBUST = {"none": FBR_PG_ROBUST_NONE, "huber": FBR_PG_ROBUST_HUBER, "cauchy": FBR_PG_ROBUST_CAUCHY}
 
 
 class FbrPgParams(_Dictable):
     _fields_ = [("max_iterations", ctypes.c_int32), ("max_pcg_iterations", ctypes.c_int32),
                 ("rel_cost_tol", ctypes.c_double), ("abs_cost_tol", ctypes.c_double), ("pcg_rel_tol", ctypes.c_double),
                 ("lambda_init", ctypes.c_double), ("lambda_factor", ctypes.c_double), ("lambda_max", ctypes.c_double),
-                ("reserved_", ctypes.c_int32 * 4)]
+                ("solver", ctypes.c_int32), ("robust", ctypes.c_int32), ("robust_scale", ctypes.c_float),
+                ("max_work_mb", ctypes.c_int32)]
 
 
 class FbrPgResult(_Dictable):
@@ -157,9 +162,14 @@ class FbrPgResult(_Dictable):
 
 def pg_params(**kw):
     """fbr_pg_params_default: 30 LM steps, 200 PCG iterations, GTSAM's 1e-5 error tolerances, PCG 1e-8,
-    lambda 1e-5 x 10 up to 1e10."""
+    lambda 1e-5 x 10 up to 1e10; the conjugate-gradient solver and no robust option.  solver and
+    robust also take their names ("direct"; "huber", "cauchy")."""
     p = FbrPgParams(30, 200, 1e-5, 1e-5, 1e-8, 1e-5, 10.0, 1e10)
     for k, v in kw.items():
+        if k == "solver" and isinstance(v, str):
+            v = PG_SOLVERS[v]
+        if k == "robust" and isinstance(v, str):
+            v = PG_ROBUST[v]
         setattr(p, k, v)
     return p
 

@@ -596,7 +596,8 @@ int fbr_pose_search(fbr_ctx* ctx, const fbr_score_params* sp, const fbr_point_xy
  * (:743-758) and correctPoses (:1735-1770), as a batch optimiser over the keyframe store, so that
  * "loop closed" can end in corrected key poses without GTSAM.  This is the project's own
  * restatement: it is pinned by a NumPy model in tests/ and not against GTSAM or iSAM2.  What stays
- * with the caller: iSAM2's incremental updates, robust kernels and IMU preintegration factors.
+ * with the caller: iSAM2's incremental updates, IMU preintegration factors and robust GPS or odometry
+ * factors (robust loop factors are below: "robust loop factors").
  * The marginal covariances of the key poses (poseCovariance, :1706) and addGPSFactor's covariance
  * gate (:1561) are below ("marginal covariances").
  *
@@ -647,7 +648,35 @@ int fbr_pose_search(fbr_ctx* ctx, const fbr_score_params* sp, const fbr_point_xy
  * asin(-R20) clamped, yaw = atan2(R10, R00); fbr_pg_apply rounds them to float.
  *
  * Two calls on the same store and factors return the same bytes: no float or double atomics, every
- * sum is taken in a fixed order. */
+ * sum is taken in a fixed order.
+ *
+ * Robust loop factors (robust != FBR_PG_ROBUST_NONE; opt-in, the default changes nothing).  They
+ * apply to the loop factors only: the between factors with |i - j| != 1, the terms of L, where a
+ * false place-recognition match arrives.  Priors, odometry and GPS factors are never re-weighted.
+ * With s = |r|^2 of a loop factor's whitened residual, e = sqrt(s) and k = robust_scale:
+ *   Huber   w = 1 if e <= k, else k / e          rho = s / 2 if e <= k, else k (e - k / 2)
+ *   Cauchy  w = 1 / (1 + s / k^2)                rho = (k^2 / 2) log1p(s / k^2)
+ * The cost is F = sum rho, with rho = s / 2 for every other factor.  A loop factor is linearised as
+ * sqrt(w) r, sqrt(w) J (w = 2 rho'(s) at the linearisation point), which is how GTSAM's
+ * noiseModel::Robust whitens.  The accept test, cost_initial, cost_final and the convergence
+ * tolerances all use this F.  A robust cost is NOT convex: the result is the local minimiser that
+ * Levenberg-Marquardt reaches from the stored poses, and a different start may end elsewhere.
+ * Huber with k = 1.345 and Cauchy with k = 3 are reasonable scales; a Cauchy scale near 1 also
+ * down-weights true loops when the drift is large.  fbr_pg_loop_weights reports s and w per loop
+ * factor, so that a caller can drop rejected loops before fbr_pg_apply and fbr_global_map_build.
+ *
+ * Direct solve (solver = FBR_PG_SOLVER_DIRECT; opt-in).  With K loop factors, U [6K x 6N] their
+ * whitened Jacobians and T the damped block-tridiagonal part, H + lambda diag(H) = T + U^T U and the
+ * step is Woodbury's, exact up to rounding whatever K:
+ *   y = T^-1 (-g),  W = T^-1 U^T,  C = I + U W = Lc Lc^T,  delta = y - W (Lc Lc^T)^-1 U y.
+ * T^-1 by the block cyclic reduction, W and C as the marginal covariances below build them (here on
+ * the damped T, once per trial), then one dense forward and backward substitution.  It needs device
+ * work space for W (6N x 6K doubles), the solve's chunk of right-hand sides per level, C and z; a need
+ * above max_work_mb returns FBR_ERR_CAPACITY before anything is allocated.  pcg_iterations is 0.  A
+ * bad pivot of T or of C ends the call with FBR_PG_NUMERICAL.  Choose it when the graph has more
+ * than a few loops: the conjugate gradients need up to 6 K + 1 iterations per solve and end at
+ * max_pcg_iterations beyond that.  Without loops the step is y and no W or C exists.  Same bytes
+ * from two calls, as above. */
 typedef struct fbr_pg_params {
   int32_t max_iterations;      /* 30 accepted LM steps */
   int32_t max_pcg_iterations;  /* 200 */
@@ -657,8 +686,17 @@ typedef struct fbr_pg_params {
   double lambda_init;          /* 1e-5 */
   double lambda_factor;        /* 10 */
   double lambda_max;           /* 1e10 */
-  int32_t reserved_[4];
+  int32_t solver;              /* FBR_PG_SOLVER_PCG 0 (the default) | FBR_PG_SOLVER_DIRECT 1 */
+  int32_t robust;              /* FBR_PG_ROBUST_NONE 0 (the default) | FBR_PG_ROBUST_HUBER 1 | FBR_PG_ROBUST_CAUCHY 2 */
+  float robust_scale;          /* k, in units of the whitened residual's norm; > 0 and finite when robust != 0 */
+  int32_t max_work_mb;         /* the direct solver's device work-space bound; 0 = 2048 */
 } fbr_pg_params;
+
+#define FBR_PG_SOLVER_PCG 0
+#define FBR_PG_SOLVER_DIRECT 1
+#define FBR_PG_ROBUST_NONE 0
+#define FBR_PG_ROBUST_HUBER 1
+#define FBR_PG_ROBUST_CAUCHY 2
 
 /* fbr_pg_result.status */
 #define FBR_PG_CONVERGED 0
@@ -707,6 +745,12 @@ int fbr_pg_optimize(fbr_ctx* ctx, const fbr_pg_params* p, fbr_pg_result* out);
 /* The last optimise's poses; *n = their count.  FBR_ERR_STATE without a result, FBR_ERR_CAPACITY
  * (with *n set) if cap < *n. */
 int fbr_pg_poses(fbr_ctx* ctx, double* poses_out /* [n][6] */, int64_t cap, int64_t* n);
+/* Every loop factor in add order at the last optimise's final poses: its index in the factor list,
+ * s = |r|^2 of its whitened residual and its weight w (1 with robust = FBR_PG_ROBUST_NONE, which makes
+ * the call a plain chi-square report).  The values are the device's, of the evaluation at the result
+ * poses.  *n = their count.  Errors as fbr_pg_poses. */
+int fbr_pg_loop_weights(fbr_ctx* ctx, int32_t* factor_index_out, double* chi2_out, double* weight_out, int64_t cap,
+                        int64_t* n);
 /* correctPoses (:1735-1770): every key pose gets its optimised x, y, z, roll, pitch, yaw rounded to
  * float through fbr_keyframes_set_pose (index and time kept).  FBR_ERR_STATE when there is no result
  * or the store has changed size since the optimise. */
@@ -719,7 +763,10 @@ int fbr_pg_apply(fbr_ctx* ctx);
  * Definition: Sigma = H^-1, H = J^T J the UNDAMPED normal matrix (lambda = 0) of every factor in the
  * list, linearised at the last optimise's poses exactly as fbr_pg_poses returns them (the double
  * Euler angles, converted back by R = Rz(yaw) Ry(pitch) Rx(roll)), so that a model reproduces the
- * point from public outputs.  The marginal of node i is the 6x6 diagonal block Sigma_ii, row-major,
+ * point from public outputs.  After a robust optimise (fbr_pg_params.robust) the loop factors carry
+ * their weights at those poses, with that optimise's kind and scale: H is that of the weighted
+ * Jacobians sqrt(w) J, so that a rejected false loop does not shrink the covariances at full
+ * weight; with robust = 0 nothing changes.  The marginal of node i is the 6x6 diagonal block Sigma_ii, row-major,
  * in the chart's tangent order [rotation; translation]; the translation part is in the body frame
  * of T_i, as GTSAM's Pose3 marginal is; entries (3,3) and (4,4) are what the reference reads.  The
  * output is exactly symmetric: r <= c is computed and mirrored.

@@ -439,6 +439,18 @@ class MapOptimization {
     }
     return r;
   }
+  /* Every loop factor in add order at the last optimise's poses: its index in the factor list, the
+   * chi-square |r|^2 of its whitened residual and its robust weight (1 without a robust option). */
+  int64_t pgLoopWeights(std::vector<int32_t>* index, std::vector<double>* chi2, std::vector<double>* weight) {
+    int64_t n = 0;
+    const int rc = fbr_pg_loop_weights(c_.get(), nullptr, nullptr, nullptr, 0, &n);
+    if (rc != FBR_OK && rc != FBR_ERR_CAPACITY) check(rc, "fbr_pg_loop_weights");
+    index->assign((size_t)n, 0);
+    chi2->assign((size_t)n, 0.0);
+    weight->assign((size_t)n, 0.0);
+    if (n > 0) check(fbr_pg_loop_weights(c_.get(), index->data(), chi2->data(), weight->data(), n, &n), "fbr_pg_loop_weights");
+    return n;
+  }
   void correctPoses() { check(fbr_pg_apply(c_.get()), "fbr_pg_apply"); }
   /* poseCovariance (:1706) of the key poses `nodes` (empty: every node, n of them) at the last
    * optimise's poses: cov [rows][36] row-major, tangent order [rotation; translation]. */

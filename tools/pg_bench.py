@@ -7,7 +7,10 @@ usage: pg_bench.py [reps] [N,N,...] [K,K,...] [K of the extra many-loops case at
        pg_bench.py --marginals [reps]   fbr_pg_marginals (every node) after an optimise, for
            (N, K) = (1000, 0), (1000, 10), (10000, 1), (10000, 200): the call time, the per-launcher
            kernel times and the CPU probe's host driver (tests/native/pg_marg_probe.cpp, one thread)
-           at the same poses, with the largest difference between the two"""
+           at the same poses, with the largest difference between the two
+       --solver pcg|direct    fbr_pg_params.solver (default pcg); the direct solver's launchers join the kernel times
+       --robust none|huber|cauchy   fbr_pg_params.robust, at the scales 1.345 / 3.0
+       --no-cpu               skip the CPU probe's host solve (minutes at N = 10,000 with many loops)"""
 import json
 import os
 import sys
@@ -19,18 +22,37 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 sys.path.insert(0, os.path.join(R, "tests"))
 from feature_base_pointcloud_registration_amd import api  # noqa: E402
-from feature_base_pointcloud_registration_amd.fbr_types import KEYPOSE, POINT_XYZI, default_params  # noqa: E402
+from feature_base_pointcloud_registration_amd.fbr_types import KEYPOSE, POINT_XYZI, default_params, pg_params  # noqa: E402
 import pg_fixtures as F  # noqa: E402
 import pg_model as PM  # noqa: E402
 
 MARGINALS = "--marginals" in sys.argv
 if MARGINALS:
     sys.argv.remove("--marginals")
+
+
+def option(name, default):
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    v = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+    return v
+
+
+SOLVER, ROBUST = option("--solver", "pcg"), option("--robust", "none")
+NO_CPU = "--no-cpu" in sys.argv
+if NO_CPU:
+    sys.argv.remove("--no-cpu")
+PG = dict(solver=SOLVER, robust=ROBUST, robust_scale={"none": 0.0, "huber": 1.345, "cauchy": 3.0}[ROBUST])
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 sizes = [int(v) for v in sys.argv[2].split(",")] if len(sys.argv) > 2 else [1000, 10000]
 loops = [int(v) for v in sys.argv[3].split(",")] if len(sys.argv) > 3 else [0, 1, 10]
 many = int(sys.argv[4]) if len(sys.argv) > 4 else 200
 NAMES = ("pg_linearize", "pg_assemble", "pg_factor", "pg_pcg", "pg_retract")
+if SOLVER == "direct":
+    NAMES = NAMES[:3] + ("pg_direct_y", "pg_marg_solve", "pg_marg_c", "pg_marg_chol", "pg_direct_z", "pg_direct_subst",
+                         "pg_direct_delta", "pg_retract")
 MARG_NAMES = ("pg_linearize", "pg_assemble", "pg_factor", "pg_selinv", "pg_marg_solve", "pg_marg_c", "pg_marg_chol",
               "pg_marg_cov")
 MARG_CASES = ((1000, 0), (1000, 10), (10000, 1), (10000, 200))
@@ -88,28 +110,29 @@ def run_marginals(ctx, n, k):
 def run(ctx, n, k):
     g = graph(n, k)
     fill(ctx, g)
-    _, r = ctx.pg_optimize()  # warm-up: allocations
+    _, r = ctx.pg_optimize(pg_params(**PG))  # warm-up: allocations
     t0 = time.perf_counter()
     for _ in range(reps):
-        ctx.pg_optimize()
+        ctx.pg_optimize(pg_params(**PG))
     wall = (time.perf_counter() - t0) / reps
     ctx.set_profiling(True, NAMES)
     before = {q: ctx.kernel_time(q) for q in NAMES}
-    ctx.pg_optimize()
+    ctx.pg_optimize(pg_params(**PG))
     kern = {}
     for q in NAMES:
         ms, cnt = ctx.kernel_time(q)
         kern[q] = {"ms": round(ms - before[q][0], 4), "launches": cnt - before[q][1]}
     ctx.set_profiling(False)
-    f = F.model_factors(g["spec"])
-    t0 = time.perf_counter()
-    _, pi = PM.probe_optimize(f, g["poses"].astype(np.float64))
-    cpu = time.perf_counter() - t0
-    out = dict(N=n, K=k, optimize_ms=round(wall * 1e3, 3), status=r["status"], lm_steps=r["iterations"], trials=r["trials"],
-               pcg_iterations=r["pcg_iterations"], cost_initial=r["cost_initial"], cost_final=r["cost_final"], kernels=kern,
-               cpu_probe_ms=round(cpu * 1e3, 3), cpu_probe=dict(status=pi["status"], lm_steps=pi["iterations"],
-                                                                 trials=pi["trials"], pcg_iterations=pi["pcg_iterations"],
-                                                                 pcg_max=pi["pcg_max"], cost_final=pi["cost_final"]))
+    out = dict(N=n, K=k, solver=SOLVER, robust=ROBUST, optimize_ms=round(wall * 1e3, 3), status=r["status"],
+               lm_steps=r["iterations"], trials=r["trials"], pcg_iterations=r["pcg_iterations"],
+               cost_initial=r["cost_initial"], cost_final=r["cost_final"], kernels=kern)
+    if not NO_CPU:  # the probe's PCG optimiser, whatever the device's solver: the scale of one CPU thread
+        f = F.model_factors(g["spec"])
+        t0 = time.perf_counter()
+        _, pi = PM.probe_optimize(f, g["poses"].astype(np.float64))
+        out["cpu_probe_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+        out["cpu_probe"] = dict(status=pi["status"], lm_steps=pi["iterations"], trials=pi["trials"],
+                                pcg_iterations=pi["pcg_iterations"], pcg_max=pi["pcg_max"], cost_final=pi["cost_final"])
     print(json.dumps(out), flush=True)
 
 
