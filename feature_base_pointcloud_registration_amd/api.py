@@ -31,8 +31,8 @@ EXPORTED_SYMBOLS = [
     "fbr_destroy", "fbr_set_map", "fbr_get_map", "fbr_project", "fbr_extract_features",
     "fbr_register", "fbr_register_trace", "fbr_process_scan", "fbr_reset_stream",
     "fbr_process_batch", "fbr_ingest_bytes", "fbr_debug_counters", "fbr_map_grid_info", "fbr_batch_stage", "fbr_batch_launch", "fbr_batch_wait",
-    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_diag_batch_cloud", "fbr_diag_knn_last", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
-    "fbr_voxel_grid", "fbr_affine_from_pose", "fbr_pose_from_affine", "fbr_selftest_math", "fbr_selftest_eigen6", "fbr_selftest_eig_certified", "fbr_selftest_voxel_order", "fbr_selftest_radix_sort",
+    "fbr_batch_flush", "fbr_batch_export_ready", "fbr_batch_results", "fbr_batch_set_full_masks", "fbr_batch_labels", "fbr_diag_batch_cloud", "fbr_diag_knn_last", "fbr_diag_gn_last", "fbr_batch_export", "fbr_batch_bytes", "fbr_set_profiling", "fbr_set_profiling_kernels", "fbr_kernel_time", "fbr_stream",
+    "fbr_voxel_grid", "fbr_affine_from_pose", "fbr_pose_from_affine", "fbr_selftest_math", "fbr_selftest_eigen6", "fbr_selftest_gn_rows", "fbr_selftest_gn_reduce", "fbr_selftest_solve6", "fbr_selftest_eig_certified", "fbr_selftest_voxel_order", "fbr_selftest_radix_sort",
     "fbr_load_map", "fbr_pcd_read", "fbr_pcd_write_ascii", "fbr_pcd_write_binary",
     "fbr_msg_to_points", "fbr_points_to_msg_data", "fbr_project_msg", "fbr_process_msg",
     "fbr_imu_convert", "fbr_imu_deskew_info", "fbr_set_deskew", "fbr_stream_copy_bandwidth", "fbr_valu_peak",
@@ -111,6 +111,9 @@ def lib():
             "fbr_selftest_math": (ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP]),
             "fbr_selftest_eigen6": (ctypes.c_int, [ctypes.c_int, _VP, _VP]),
             "fbr_selftest_eig_certified": (ctypes.c_int, [ctypes.c_int, _VP, ctypes.c_float, _VP]),
+            "fbr_selftest_gn_rows": (ctypes.c_int, [ctypes.c_int, _VP, _VP]),
+            "fbr_selftest_gn_reduce": (ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP]),
+            "fbr_selftest_solve6": (ctypes.c_int, [ctypes.c_int, _VP, _VP, _VP, _VP, _VP]),
             "fbr_selftest_voxel_order": (ctypes.c_int, [_I64, _VP, ctypes.c_int, _VP]),
             "fbr_selftest_radix_sort": (ctypes.c_int, [_I64, ctypes.c_int, ctypes.c_int, _VP, _VP]),
             "fbr_load_map": (ctypes.c_int, [_VP, ctypes.c_char_p, ctypes.c_char_p]),
@@ -283,6 +286,43 @@ def selftest_eigen6(mats):
     _check(lib().fbr_selftest_eigen6(len(a), ptr(a), ptr(out)), "fbr_selftest_eigen6")
     n = len(a)
     return ((out[:, :6], out[:, 6:42].reshape(n, 6, 6)), (out[:, 42:48], out[:, 48:].reshape(n, 6, 6)))
+
+
+def selftest_gn_rows(cases):
+    """The residual pass's per-query functions on the device (fbr_selftest_gn_rows): cases (n, 28)
+    float32 = kind, 5 neighbours xyz, query xyz, scan point xyz, trig[6]; returns a dict of fit_ok
+    (n,) bool, fit (n, 6), ok (n,) bool, coeff (n, 4), row (n, 6), b (n,)."""
+    a = np.ascontiguousarray(cases, np.float32).reshape(-1, 28)
+    out = np.zeros((len(a), 20), np.float32)
+    _check(lib().fbr_selftest_gn_rows(len(a), ptr(a), ptr(out)), "fbr_selftest_gn_rows")
+    return dict(fit_ok=out[:, 0] != 0, fit=out[:, 1:7].copy(), ok=out[:, 7] != 0, coeff=out[:, 8:12].copy(),
+                row=out[:, 12:18].copy(), b=out[:, 18].copy())
+
+
+def selftest_gn_reduce(rows, b, ok):
+    """res_reduce on the device (fbr_selftest_gn_reduce): rows (s, 256, 6), b (s, 256), ok (s, 256)
+    -> (s, 28) float64 sums (21 upper AtA products, 6 AtB, the count)."""
+    rows = np.asarray(rows, np.float32).reshape(-1, 256, 6)
+    packed = np.ascontiguousarray(np.concatenate([rows, np.asarray(b, np.float32).reshape(-1, 256, 1)], axis=2))
+    okf = np.ascontiguousarray(np.asarray(ok).reshape(-1, 256) != 0, np.int8)
+    assert len(okf) == len(packed)
+    out = np.zeros((len(packed), 32), np.float64)
+    _check(lib().fbr_selftest_gn_reduce(len(packed), ptr(packed), ptr(okf), ptr(out)), "fbr_selftest_gn_reduce")
+    assert not out[:, 28:].any()
+    return out[:, :28].copy()
+
+
+def selftest_solve6(mats, rhs):
+    """qr_solve6 and lu_inv6 on the device (fbr_selftest_solve6): mats (n, 6, 6), rhs (n, 6) ->
+    (qr return codes (n,), x (n, 6), lu return codes (n,), inverses (n, 6, 6))."""
+    a = np.ascontiguousarray(mats, np.float32).reshape(-1, 36)
+    b = np.ascontiguousarray(rhs, np.float32).reshape(-1, 6)
+    assert len(a) == len(b)
+    x = np.zeros((len(a), 6), np.float32)
+    inv = np.zeros((len(a), 36), np.float32)
+    ret = np.zeros((len(a), 2), np.int32)
+    _check(lib().fbr_selftest_solve6(len(a), ptr(a), ptr(b), ptr(x), ptr(inv), ptr(ret)), "fbr_selftest_solve6")
+    return ret[:, 0].copy(), x, ret[:, 1].copy(), inv.reshape(-1, 6, 6)
 
 
 def selftest_eig_certified(mats, thr=100.0):
@@ -1039,6 +1079,33 @@ class Context:
         names = ("iterations", "r", "rx", "flat", "sparse", "lpq", "fused", "tiles")
         return dict(n_corner=nc.value, n_surf=ns.value, queries=q[:n].copy(), nbr=nbr[:n].copy(),
                     desc={k: int(v) for k, v in zip(names, desc)})
+
+    def diag_gn_last(self):
+        """Diagnostic: the residual pass behind diag_knn_last's search (fbr_diag_gn_last).  Returns a
+        dict: n_corner / n_surf; per query in diag_knn_last's order points (n, 3) float32 (the
+        down-sampled scan-frame point), fit_state (n,) int8 (0 none, 1
+        fitted, 2 rejected), fit (n, 6) float32, nsame (n,) int8 (-1 everywhere: the fused pass keeps
+        none); per work item items (m, 4) int32 {job, kind, first query, queries} and partial (m, 32)
+        float64; T (12,) and trig (6,) the pass ran at."""
+        f = lib().fbr_diag_gn_last
+        f.restype = ctypes.c_int
+        f.argtypes = [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _I64, _VP]
+        nc, ns, ni = _I32(), _I32(), _I32()
+        _check(f(self._h, ctypes.byref(nc), ctypes.byref(ns), None, None, None, None, 0, ctypes.byref(ni), None, None, 0,
+                 None),
+               "fbr_diag_gn_last")
+        n, m = nc.value + ns.value, ni.value
+        state, same = np.zeros(max(n, 1), np.int8), np.zeros(max(n, 1), np.int8)
+        fit, pts = np.zeros((max(n, 1), 6), np.float32), np.zeros((max(n, 1), 3), np.float32)
+        items = np.zeros((max(m, 1), 4), np.int32)
+        partial = np.zeros((max(m, 1), 32), np.float64)
+        tt = np.zeros(18, np.float32)
+        _check(f(self._h, ctypes.byref(nc), ctypes.byref(ns), ptr(pts), ptr(state), ptr(fit), ptr(same), max(n, 1),
+                 ctypes.byref(ni),
+                 ptr(items), ptr(partial), max(m, 1), ptr(tt)), "fbr_diag_gn_last")
+        return dict(n_corner=nc.value, n_surf=ns.value, points=pts[:n].copy(), fit_state=state[:n].copy(), fit=fit[:n].copy(),
+                    nsame=same[:n].copy(), items=items[:m].copy(), partial=partial[:m].copy(), T=tt[:12].copy(),
+                    trig=tt[12:].copy())
 
     def diag_force_capacity_error(self, job):
         """Diagnostic: batch job `job` of the following launches is reported as over the feature

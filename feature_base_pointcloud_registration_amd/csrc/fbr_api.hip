@@ -188,7 +188,7 @@ int fbr_create(fbr_ctx** out, const fbr_params* p, int hip_device) {
               dalloc(c->d_iter_cnt, kMaxSub * 4 * std::max(1, p->max_iterations)) ||
               dalloc(c->d_feat_scratch, Bw * H * feat_slot_bytes(c->W)) ||
               c->iter_flags.alloc(kMaxSub * (std::max(1, p->max_iterations) + 1)) || dalloc(c->d_pose_out, Bw * 6) ||
-              dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6 + 12) ||
+              dalloc(c->d_stats, Bw) || dalloc(c->d_trace, Bw * p->max_iterations * 6 + 18) ||
               dalloc(c->d_desk_mode, B) || dalloc(c->d_rowmin, Bw * H) || dalloc(c->d_result, B) ||
               dalloc(c->d_choff, Bw * H * (c->W / 32 + 1)) ||
               dalloc(c->h_result, B) || dalloc(c->h_scan, c->NMAX) || dalloc(c->h_nin, 1) || dalloc(c->h_crop, 2) ||
@@ -367,6 +367,81 @@ extern "C" int fbr_diag_knn_last(fbr_ctx* c, int32_t* n_corner, int32_t* n_surf,
       const int32_t* o = raw.data() + (size_t)it * 5 * 256 + slot;
       if (o[0] < 0) continue;
       for (int k = 0; k < 5; ++k) nbr[5 * q + k] = o[k * 256];
+    }
+  }
+  return FBR_OK;
+}
+
+// Diagnostic (tests): the residual pass behind fbr_diag_knn_last's search, decoded the same way: the
+// scan-frame point and the fit cache (GnArgs::fits / fitc / nsame) per query in that call's order, the job's work items with
+// their normal-equation partials, and the transform and trig k_gn_solve kept before its step.
+extern "C" int fbr_diag_gn_last(fbr_ctx* c, int32_t* n_corner, int32_t* n_surf, float* points, int8_t* fit_state,
+                                float* fit, int8_t* nsame, int64_t cap, int32_t* n_items, int32_t* items,
+                                double* partial, int64_t item_cap, float* T_trig) {
+  if (!c || cap < 0 || item_cap < 0 || (cap && (!points || !fit_state || !fit || !nsame)) ||
+      (item_cap && (!items || !partial)))
+    return FBR_ERR_INVALID_ARG;
+  if (!c->knn_last_valid) return FBR_ERR_STATE;
+  CK(enter(c));
+  CK(fbr_sync(c->stream));
+  GnState g;
+  int32_t ncs[2], range[2];
+  CK(fbr_memcpy_sync(&g, c->d_gn, sizeof(g), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(&ncs[0], c->d_ncds, sizeof(int32_t), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(&ncs[1], c->d_nsds, sizeof(int32_t), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(range, c->d_item_range, sizeof(range), hipMemcpyDeviceToHost));
+  const int pass = g.iter - 1;
+  const int ni = pass >= 0 ? std::max(0, range[1] - range[0]) : 0;
+  if (ni && (range[0] < 0 || range[1] > c->max_items)) return FBR_ERR_STATE;
+  if (n_corner) *n_corner = ncs[0];
+  if (n_surf) *n_surf = ncs[1];
+  if (n_items) *n_items = ni;
+  if (T_trig) {
+    if (pass >= 0) {
+      CK(fbr_memcpy_sync(T_trig, c->knn_T_slot(), sizeof(float) * 18, hipMemcpyDeviceToHost));
+    } else {  // no pass ran: the guess's
+      std::memcpy(T_trig, g.T, sizeof(g.T));
+      std::memcpy(T_trig + 12, g.trig, sizeof(g.trig));
+    }
+  }
+  const int64_t n = (int64_t)ncs[0] + ncs[1];
+  if (!cap && !item_cap) return FBR_OK;
+  if ((cap && cap < n) || (item_cap && item_cap < ni)) return FBR_ERR_CAPACITY;
+  const bool fused = pass >= 0 && pass < (int)c->knn_desc.size() && c->knn_desc[pass].fused;
+  if (cap) {
+    std::vector<float4> pts((size_t)std::max<int64_t>(n, 1));
+    if (ncs[0]) CK(fbr_memcpy_sync(pts.data(), c->d_cornerDS, sizeof(float4) * ncs[0], hipMemcpyDeviceToHost));
+    if (ncs[1]) CK(fbr_memcpy_sync(pts.data() + ncs[0], c->d_surfDS, sizeof(float4) * ncs[1], hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) {
+      points[3 * i] = pts[i].x;
+      points[3 * i + 1] = pts[i].y;
+      points[3 * i + 2] = pts[i].z;
+      fit_state[i] = 0;
+      nsame[i] = fused ? -1 : 0;
+      for (int k = 0; k < 6; ++k) fit[6 * i + k] = 0.0f;
+    }
+  }
+  if (!ni) return FBR_OK;
+  std::vector<int4> its((size_t)ni);
+  CK(fbr_memcpy_sync(its.data(), c->d_items + range[0], sizeof(int4) * ni, hipMemcpyDeviceToHost));
+  if (item_cap) {
+    std::memcpy(items, its.data(), sizeof(int4) * ni);
+    CK(fbr_memcpy_sync(partial, c->d_partial + (int64_t)range[0] * 32, sizeof(double) * 32 * ni, hipMemcpyDeviceToHost));
+  }
+  if (!cap) return FBR_OK;
+  std::vector<float> fc((size_t)ni * 6 * 256);
+  std::vector<int8_t> fs((size_t)ni * 256), sm((size_t)ni * 256);
+  CK(fbr_memcpy_sync(fc.data(), c->d_fitc + (int64_t)range[0] * 6 * 256, sizeof(float) * fc.size(), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(fs.data(), c->d_fits + (int64_t)range[0] * 256, fs.size(), hipMemcpyDeviceToHost));
+  CK(fbr_memcpy_sync(sm.data(), c->d_nsame + (int64_t)range[0] * 256, sm.size(), hipMemcpyDeviceToHost));
+  for (int it = 0; it < ni; ++it) {
+    const int4 item = its[it];  // {job, 0 corner / 1 surf, first query, queries}
+    for (int slot = 0; slot < item.w && slot < 256; ++slot) {
+      const int64_t q = (item.y == 0 ? 0 : ncs[0]) + item.z + slot;
+      if (item.x != 0 || q < 0 || q >= n) return FBR_ERR_STATE;
+      fit_state[q] = fs[(size_t)it * 256 + slot];
+      if (!fused) nsame[q] = sm[(size_t)it * 256 + slot];
+      for (int k = 0; k < 6; ++k) fit[6 * q + k] = fc[((size_t)it * 6 + k) * 256 + slot];
     }
   }
   return FBR_OK;

@@ -372,13 +372,14 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   bool crop_cached = false;  // d_cropcnt holds the staged batch's CropBox statistics
   Dev<float> d_pose_out;
   Dev<fbr_reg_stats> d_stats;
-  Dev<float> d_trace;  // [Bwork][max_iterations][6] traced poses, then knn_T_slot's 12 floats
+  Dev<float> d_trace;  // [Bwork][max_iterations][6] traced poses, then knn_T_slot's 12 + 6 floats
   Dev<JobResult> d_result;     // [Bcap] packed per-job results
   Pinned<JobResult> h_result;  // [Bcap]
   std::vector<int32_t> last_iters, last_q, last_n, last_m;
   // fbr_diag_knn_last: the kernel every iteration's kNN pass of a single scan ran, and whether the
-  // latest run was a single scan (job slot 0 then holds it); the pass's transform (GnArgs::knn_T)
-  // is kept behind the traced poses (knn_T_slot: no device block of its own)
+  // latest run was a single scan (job slot 0 then holds it); the pass's transform and trig
+  // (GnArgs::knn_T, 12 + 6 floats: fbr_diag_gn_last reads both) are kept behind the traced poses
+  // (knn_T_slot: no device block of its own)
   float* knn_T_slot() { return d_trace + Bwork * std::max(0, P.max_iterations) * 6; }
   std::vector<KnnLaunchDesc> knn_desc;  // [max_iterations]
   bool knn_last_valid = false;

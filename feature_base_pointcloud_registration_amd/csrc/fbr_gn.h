@@ -466,8 +466,10 @@ __device__ void gn_solve_job(const GnArgs& a, int job, const double* acc, float*
   g.iter = iterCount + 1;
   const int sel = (int)acc[27];
   g.n_sel = sel;
-  if (a.knn_T)  // diagnostic read-back: the transform this iteration's kNN pass ran at
+  if (a.knn_T) {  // diagnostic read-back: the transform and the trig this iteration's passes ran at
     for (int k = 0; k < 12; ++k) a.knn_T[job * 12 + k] = g.T[k];
+    for (int k = 0; k < 6; ++k) a.knn_T[a.B * 12 + job * 6 + k] = g.trig[k];
+  }
   if (a.trace) {
     // filled below after the update; pre-fill with the current pose for the early-return case
     for (int k = 0; k < 6; ++k) a.trace[((int64_t)job * a.max_iter + iterCount) * 6 + k] = g.pose[k];

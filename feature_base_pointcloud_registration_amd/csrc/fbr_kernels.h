@@ -413,8 +413,9 @@ struct GnArgs {
   const int32_t* ferr;
   const int32_t* cropcnt;
   // Single scans (diagnostic, fbr_diag_knn_last): k_gn_solve keeps the transform the iteration's
-  // kNN pass ran at, GnState::T before the step, here ([B][12]); null: not kept.  Last member: the
-  // kernels that do not read it keep their argument offsets.
+  // kNN pass ran at, GnState::T before the step, here ([B][12]), and behind it the residual pass's
+  // GnState::trig ([B][6], fbr_diag_gn_last); null: not kept.  Last member: the kernels that do not
+  // read it keep their argument offsets.
   float* knn_T;
 };
 // Which kernel the latest kNN launch of this thread ran (written by the host launchers of

@@ -4,12 +4,15 @@
 // correctly rounded f32 sqrt and division (SSE sqrtss / divss), glibc atan2f
 // (imageProjection.cpp:605,618) and glibc sinf / cosf (pcl::getTransformation, LMOptimization
 // mapOptmization.h:1259-1264).  tests/test_gpu_parity.py feeds random operands through this
-// kernel and compares every output bit with the host.  Also here: the selftests of the introsort
+// kernel and compares every output bit with the host.  Also here: the per-query functions of the
+// Gauss-Newton residual pass, its workgroup reduction and the 6x6 solvers on caller-given inputs
+// (fbr_selftest_gn_rows / _gn_reduce / _solve6, tests/test_gn_rows.py), the selftests of the introsort
 // partition phase and of the wave-chunk radix sorts (fbr_vg_sort.h), and the bandwidth / VALU probes.
 #include <algorithm>
 
 #include "fbr_common.h"
 #include "fbr_fdlibm.h"
+#include "fbr_gn.h"
 #include "fbr_sincosf.h"
 #include "fbr_introsort.h"
 #include "fbr_solvers.h"
@@ -57,6 +60,66 @@ __global__ void __launch_bounds__(64) k_selftest_eigen6(const float* a, float* o
 __global__ void k_selftest_eig_cert(int n, const float* a, float thr, int32_t* out) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m < n) out[m] = eig_above_certified<6>(a + (int64_t)m * 36, thr) ? 1 : 0;
+}
+
+// One lane per case: fbr_gn.h's fits, residual coefficients and LMOptimization row on caller-given
+// neighbours, query, scan point and trig (fbr_selftest_gn_rows; layouts in include/fbr.h).
+constexpr int kGnRowsIn = 28, kGnRowsOut = 20;
+__global__ void k_selftest_gn_rows(int n, const float* in, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* c = in + (int64_t)kGnRowsIn * i;
+  float* o = out + (int64_t)kGnRowsOut * i;
+  const bool corner = c[0] == 0.0f;
+  Nbr5 nn;
+  for (int j = 0; j < 5; ++j) { nn.x[j] = c[1 + 3 * j]; nn.y[j] = c[2 + 3 * j]; nn.z[j] = c[3 + 3 * j]; }
+  const float x0 = c[16], y0 = c[17], z0 = c[18];
+  const float4 p = make_float4(c[19], c[20], c[21], 0.0f);
+  GnState g{};
+  for (int k = 0; k < 6; ++k) g.trig[k] = c[22 + k];
+  float fit[6] = {0, 0, 0, 0, 0, 0}, row[6] = {0, 0, 0, 0, 0, 0}, b = 0.0f;
+  float4 coeff = make_float4(0, 0, 0, 0);
+  const bool fit_ok = corner ? corner_fit(nn, fit) : surf_fit(nn, fit);
+  bool ok = false;
+  if (fit_ok) {
+    corner ? corner_apply(fit, x0, y0, z0, coeff) : surf_apply(fit, x0, y0, z0, coeff);
+    ok = res_apply_row(g, corner, fit, p, x0, y0, z0, row, b);
+  }
+  o[0] = fit_ok ? 1.0f : 0.0f;
+  for (int k = 0; k < 6; ++k) o[1 + k] = fit_ok ? fit[k] : 0.0f;
+  o[7] = ok ? 1.0f : 0.0f;
+  o[8] = coeff.x; o[9] = coeff.y; o[10] = coeff.z; o[11] = coeff.w;
+  for (int k = 0; k < 6; ++k) o[12 + k] = row[k];
+  o[18] = b;
+  o[19] = 0.0f;
+}
+
+// One 256-thread workgroup per set of rows: res_reduce as gn_residual_item calls it (a lane
+// without an accepted row passes zeros).
+__global__ void __launch_bounds__(kResThreads) k_selftest_gn_reduce(const float* rows, const int8_t* okf, double* out) {
+  __shared__ double red[kResThreads / 64][28];
+  const int tid = threadIdx.x;
+  const int64_t q = (int64_t)blockIdx.x * kResThreads + tid;
+  float row[6] = {0, 0, 0, 0, 0, 0}, b = 0.0f;
+  const bool ok = okf[q] != 0;
+  if (ok) {
+    for (int k = 0; k < 6; ++k) row[k] = rows[q * 7 + k];
+    b = rows[q * 7 + 6];
+  }
+  res_reduce(red, tid, row, b, ok, out + (int64_t)blockIdx.x * kPartial);
+}
+
+// One lane per 6x6 system: qr_solve6 and lu_inv6.
+__global__ void k_selftest_solve6(int n, const float* a, const float* b, float* x, float* inv, int32_t* ret) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float A[36], X[6], Bi[36];
+  for (int k = 0; k < 36; ++k) A[k] = a[(int64_t)36 * i + k];
+  for (int k = 0; k < 6; ++k) X[k] = b[(int64_t)6 * i + k];
+  ret[2 * i + 1] = lu_inv6(A, Bi);
+  ret[2 * i] = qr_solve6(A, X);
+  for (int k = 0; k < 6; ++k) x[(int64_t)6 * i + k] = X[k];
+  for (int k = 0; k < 36; ++k) inv[(int64_t)36 * i + k] = Bi[k];
 }
 
 // std::sort's partition phase (fbr_introsort.h) on one array: lds = 0 keeps everything in global
@@ -295,6 +358,70 @@ extern "C" int fbr_selftest_eigen6(int n, const float* a, float* out) {
   }
   (void)hipFree(da);
   (void)hipFree(dout);
+  return rc;
+}
+
+extern "C" int fbr_selftest_gn_rows(int n, const float* in, float* out) {
+  if (n <= 0 || !in || !out) return FBR_ERR_INVALID_ARG;
+  float *din = nullptr, *dout = nullptr;
+  const size_t bi = sizeof(float) * fbr::kGnRowsIn * n, bo = sizeof(float) * fbr::kGnRowsOut * n;
+  int rc = FBR_OK;
+  if (hipMalloc(&din, bi) != hipSuccess || hipMalloc(&dout, bo) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else if (hipMemcpy(din, in, bi, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else {
+    hipLaunchKernelGGL(fbr::k_selftest_gn_rows, dim3((n + 63) / 64), dim3(64), 0, 0, n, din, dout);
+    if (hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost) != hipSuccess) rc = FBR_ERR_HIP;
+  }
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return rc;
+}
+
+extern "C" int fbr_selftest_gn_reduce(int n_sets, const float* rows, const int8_t* ok, double* out) {
+  if (n_sets <= 0 || !rows || !ok || !out) return FBR_ERR_INVALID_ARG;
+  float* drows = nullptr;
+  int8_t* dok = nullptr;
+  double* dout = nullptr;
+  const size_t nq = (size_t)n_sets * fbr::kResThreads, bo = sizeof(double) * fbr::kPartial * n_sets;
+  int rc = FBR_OK;
+  if (hipMalloc(&drows, sizeof(float) * 7 * nq) != hipSuccess || hipMalloc(&dok, nq) != hipSuccess ||
+      hipMalloc(&dout, bo) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else if (hipMemcpy(drows, rows, sizeof(float) * 7 * nq, hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(dok, ok, nq, hipMemcpyHostToDevice) != hipSuccess || hipMemset(dout, 0, bo) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else {
+    hipLaunchKernelGGL(fbr::k_selftest_gn_reduce, dim3(n_sets), dim3(fbr::kResThreads), 0, 0, drows, dok, dout);
+    if (hipMemcpy(out, dout, bo, hipMemcpyDeviceToHost) != hipSuccess) rc = FBR_ERR_HIP;
+  }
+  (void)hipFree(drows);
+  (void)hipFree(dok);
+  (void)hipFree(dout);
+  return rc;
+}
+
+extern "C" int fbr_selftest_solve6(int n, const float* a, const float* b, float* x, float* inv, int32_t* ret) {
+  if (n <= 0 || !a || !b || !x || !inv || !ret) return FBR_ERR_INVALID_ARG;
+  float *da = nullptr, *db = nullptr, *dx = nullptr, *di = nullptr;
+  int32_t* dr = nullptr;
+  const size_t b36 = sizeof(float) * 36 * n, b6 = sizeof(float) * 6 * n, br = sizeof(int32_t) * 2 * n;
+  int rc = FBR_OK;
+  if (hipMalloc(&da, b36) != hipSuccess || hipMalloc(&db, b6) != hipSuccess || hipMalloc(&dx, b6) != hipSuccess ||
+      hipMalloc(&di, b36) != hipSuccess || hipMalloc(&dr, br) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else if (hipMemcpy(da, a, b36, hipMemcpyHostToDevice) != hipSuccess ||
+             hipMemcpy(db, b, b6, hipMemcpyHostToDevice) != hipSuccess) {
+    rc = FBR_ERR_HIP;
+  } else {
+    hipLaunchKernelGGL(fbr::k_selftest_solve6, dim3((n + 63) / 64), dim3(64), 0, 0, n, da, db, dx, di, dr);
+    if (hipMemcpy(x, dx, b6, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(inv, di, b36, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(ret, dr, br, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = FBR_ERR_HIP;
+  }
+  for (void* q : {(void*)da, (void*)db, (void*)dx, (void*)di, (void*)dr}) (void)hipFree(q);
   return rc;
 }
 

@@ -1019,6 +1019,21 @@ typedef struct fbr_knn_desc {
 } fbr_knn_desc;
 int fbr_diag_knn_last(fbr_ctx* ctx, int32_t* n_corner, int32_t* n_surf, float* queries /* [cap][3] */,
                       int32_t* nbr /* [cap][5] */, int64_t cap, fbr_knn_desc* desc);
+/* Diagnostic (tests): the residual pass that followed that search, under the same preconditions.
+ * Per query, in fbr_diag_knn_last's order: points[3 i ..] the down-sampled scan-frame point the
+ * query was transformed from, fit_state (0 none, 1 fitted, 2 rejected by the eigenvalue
+ * / plane gate) and fit[6 i ..] of the query's fit cache (corner: two line points; surf: pa, pb, pc,
+ * pd and two unused floats), nsame 1 where the search found the previous pass's five neighbours and
+ * the cached fit was reused (-1 for every query when the pass ran fused with the search, which keeps
+ * no such flag).  Per work item of the job: items[4 k ..] = {job, 0 corner / 1 surf, first query,
+ * queries} and partial[32 k ..] its normal-equation partial (21 upper AtA entries, 6 AtB, the row
+ * count, 4 zero pads).  T_trig (may be NULL): T[12] and trig[6] the pass ran at.  cap = 0 and
+ * item_cap = 0 return the counts only; FBR_ERR_CAPACITY when a non-zero capacity is too small. */
+int fbr_diag_gn_last(fbr_ctx* ctx, int32_t* n_corner, int32_t* n_surf, float* points /* [cap][3] */,
+                     int8_t* fit_state /* [cap] */, float* fit /* [cap][6] */, int8_t* nsame /* [cap] */, int64_t cap,
+                     int32_t* n_items,
+                     int32_t* items /* [item_cap][4] */, double* partial /* [item_cap][32] */, int64_t item_cap,
+                     float* T_trig /* [18] */);
 /* Enqueue (on the ctx stream, after every launch in flight) a copy of the latest launch's per-job
  * pose records {pose[6] f32, iterations i32, status i32} = 32 B/job into `device_dst` (device
  * memory of the ctx's device, [n_jobs][8] x 4 B) — the payload of the cross-GPU pose all-gather. */
@@ -1099,6 +1114,21 @@ int fbr_selftest_math(int n, const float* a, const float* b, float* out);
  * mapOptmization.h:1353) by the single-lane and the wave-parallel device Jacobi; out[84i..] =
  * {6 eigenvalues, 36 eigenvector entries} of each (tests compare both with the host restatement). */
 int fbr_selftest_eigen6(int n, const float* a, float* out);
+
+/* Diagnostic: the per-query functions of the Gauss-Newton residual pass, one lane per case.
+ * in[28 i ..] = {kind (0 corner, 1 surf), five neighbours x y z, the map-frame query x y z, the
+ * scan-frame point x y z, trig[6]}; out[20 i ..] = {fit ok, fit[6], apply ok, coeff[4], row[6], b,
+ * 0}: corner_fit / surf_fit, corner_apply / surf_apply and the LMOptimization row of the product
+ * (mapOptmization.h:1016-1211, :1286-1332).  Whatever a rejected stage would have written is 0. */
+int fbr_selftest_gn_rows(int n, const float* in, float* out);
+/* Diagnostic: the workgroup reduction of the item partials.  Set s holds 256 rows rows[(256 s + t)
+ * * 7 ..] = {row[6], b} with flags ok[256 s + t] (a slot whose flag is 0 contributes nothing);
+ * out[32 s ..] = the 28 sums (21 upper AtA products, 6 AtB, the count) and 4 zero pads. */
+int fbr_selftest_gn_reduce(int n_sets, const float* rows, const int8_t* ok, double* out);
+/* Diagnostic: cv::solve(A, b, DECOMP_QR) and Mat::inv (LU) on n 6x6 float systems, one lane each:
+ * a[36 i ..], b[6 i ..] -> x[6 i ..] and inv[36 i ..]; ret[2 i ..] = the two return codes (0:
+ * singular, the corresponding output is then unspecified). */
+int fbr_selftest_solve6(int n, const float* a, const float* b, float* x, float* inv, int32_t* ret);
 
 /* Diagnostic: the degeneracy fast path of the iteration-0 solve.  out[i] = 1 when every eigenvalue
  * of the symmetric 6x6 float matrix a[36i..36i+35] is certified above thr (LDL^T of A - (thr +

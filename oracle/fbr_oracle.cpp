@@ -1564,6 +1564,7 @@ int orc_imu_deskew_info(const fbr_imu_sample* q, int64_t n, double timeScanCur, 
 // Small-solver probes for unit tests.
 void orc_jacobi(float* A, int n, float* W, float* V) { cv_jacobi(A, n, W, V); }
 int orc_qr_solve(float* A, int n, float* b) { return cv_qr_solve(A, n, b); }
+int orc_lu_inv(const float* A, int n, float* Binv) { return cv_lu_inv(A, n, Binv); }
 void orc_colpiv_solve(const float* A15, const float* b5, float* x3) {
   float A[5][3];
   std::memcpy(A, A15, sizeof(A));

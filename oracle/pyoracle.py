@@ -64,6 +64,7 @@ def lib():
         L.orc_pose_from_affine.argtypes = [_VP, _VP]
         L.orc_jacobi.argtypes = [_VP, ctypes.c_int, _VP, _VP]
         L.orc_qr_solve.argtypes = [_VP, ctypes.c_int, _VP]
+        L.orc_lu_inv.argtypes = [_VP, ctypes.c_int, _VP]
         L.orc_colpiv_solve.argtypes = [_VP, _VP, _VP]
         L.orc_knn5.argtypes = [_VP, _I64, _VP, _I64, _VP, _VP]
         L.orc_sort_smoothness.argtypes = [_VP, _I64, _VP]

@@ -1036,7 +1036,9 @@ def test_wave_ring_filter_is_bit_identical_to_workgroup_kernel():
     ({"FBR_KNN_LPQ": "8"}, False),                             # wide mode for every launch
     ({"FBR_GN_TAIL": "1"}, False),                             # fused kNN + residual (tail mode throughout)
     ({"FBR_KNN_FLAT": "0"}, False),                            # per-row loop from iteration 1
-], ids=["cells-0.5", "cells-0.5-sparse", "wide", "fused", "no-flat"])
+    ({"FBR_FIT_CACHE": "0"}, False),                           # every fit recomputed
+    ({"FBR_FIT_CACHE": "0", "FBR_GN_TAIL": "1"}, False),       # the same in the fused kernel
+], ids=["cells-0.5", "cells-0.5-sparse", "wide", "fused", "no-flat", "no-fit-cache", "no-fit-cache-fused"])
 def test_knn_variants_are_bit_identical(c2_map, env, sparse):
     """Every kNN variant (cell sizes, grid layouts, wide / fused / per-row launches) selects the
     same neighbour sets: poses and stats of 12 C2 jobs equal the default path's bit for bit."""
