@@ -165,7 +165,8 @@ struct FeatArgs {
   // tests only (fbr_diag_feature_paths), null in normal launches: [B][H] one word per ring, which
   // walk each segment j took: bits 4j..4j+1 corner (0 one word, 1 two words, 2 member-indexed,
   // 3 stale-slot walk), bits 4j+2..4j+3 surf (0 skipped, 1 window, 2 whole walk after the window
-  // left a member near ep undecided, 3 whole walk), bit 24+j: segment j is not empty.
+  // left a member near ep undecided, 3 whole walk), bit 24+j: segment j is not empty, bits 30..31:
+  // the k_features instance that ran (1: WMAX 5, 2: WMAX 6, 3: WMAX 12).
   uint32_t* paths = nullptr;
 };
 size_t features_lds_bytes(const FeatArgs& a, int nwv);  // nwv: waves per ring

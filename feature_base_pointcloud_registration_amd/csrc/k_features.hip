@@ -1561,7 +1561,7 @@ k_features(FeatArgs a) {
   if constexpr (NWV > 1) __syncthreads();
   write_outputs<NT>(S, a, rg, a.label + job * HW, cb, ca, tid);
   if (tid == 0) a.corner_cnt[slot] = corner_cnt;
-  if (tid == 0 && a.paths) a.paths[slot] = rec;
+  if (tid == 0 && a.paths) a.paths[slot] = rec | (WMAX == 5 ? 1u : WMAX == 6 ? 2u : 3u) << 30;  // the instance
   tm.mark(9);
   if constexpr (kStamps) {
     if (tid == 0 && a.stamps)

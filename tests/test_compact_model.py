@@ -8,8 +8,9 @@ restates the kernels' index arithmetic (tile shapes, chunk-offset writes, the XC
 and checks, over many (H, W) shapes and owner densities, that every launched tile maps to a
 valid job, every chunk offset k_compact reads was written by k_rowcount, and the destinations
 are exactly the row-major compaction positions (a permutation inside [0, n_valid)).  The device
-kernels themselves are compared bit-exact with the oracle by the GPU tests
-(test_gpu_parity.py::test_projection_*).
+kernels themselves are compared bit-exact with the oracle by the GPU tests: the benchmark configs
+in test_gpu_parity.py::test_projection_*, and the shapes this model names as edges (a single ring,
+ragged row blocks and chunks, CG > 64, tiles above 512 cells) in test_frontend_shapes.py.
 """
 import numpy as np
 import pytest

@@ -287,3 +287,141 @@ def test_deskew_tables_after_a_record_stage_require_restaging():
         p1, s1 = ctx.batch_results()
         p2, s2 = ctx.process_batch(scans, guesses)
     assert np.array_equal(p1.view(np.int32), p2.view(np.int32)) and s1.tobytes() == s2.tobytes()
+
+
+# ------------------------------------------------------------------------------- find_rotation's edges
+# deskew_point / find_rotation on the device (k_compact<true>) where the in-order synthetic scans
+# above never go: point times before the first IMU sample, exactly on samples, on and past the last
+# one; tables of two samples and of nearly queueLength; transStartInverse from a first deskewed
+# point that is not input point 0.  The shapes add a single ring, ragged row blocks and W = 4000.
+EDGE_SHAPES = [(16, 1800), (1, 1800), (40, 1800), (6, 4000)]
+EDGE_TABLES = {"two-samples": 1, "twenty": 20, "near-capacity": IMU_QUEUE - 2}  # imu_pointer_cur
+EDGE_TCUR = 20.0
+BRANCHES = ["before_first", "on_sample", "between", "on_last", "past_last"]
+
+
+def edge_sample_times(cur):
+    """Relative times of the table's cur + 1 samples, as float32: EDGE_TCUR + the value is exact in
+    double, so a point whose float `time` is one of them lies exactly on that sample."""
+    s = np.linspace(0.0125, 0.09, cur + 1).astype(np.float32)
+    assert (np.diff(s) > 0).all() and ((EDGE_TCUR + s.astype(np.float64)) - EDGE_TCUR == s.astype(np.float64)).all()
+    return s
+
+
+def edge_table(cur):
+    """A deskewInfo table written by hand: imuTime on edge_sample_times, imuRot a smooth rotation
+    from 0 (imuDeskewInfo starts its integration at zero, :355-360)."""
+    s = edge_sample_times(cur).astype(np.float64)
+    t = np.zeros(1, DESKEW_TABLE)[0]
+    t["status"], t["imu_available"], t["imu_pointer_cur"] = FBR_DESKEW_READY, 1, cur
+    t["imu_roll_init"], t["imu_pitch_init"], t["imu_yaw_init"] = 0.01, -0.02, 0.3
+    t["time_scan_cur"] = EDGE_TCUR
+    t["imu_time"][:cur + 1] = EDGE_TCUR + s
+    d = s - s[0]
+    t["imu_rot_x"][:cur + 1] = 0.4 * d + 0.8 * d * d
+    t["imu_rot_y"][:cur + 1] = -0.3 * d
+    t["imu_rot_z"][:cur + 1] = 1.5 * d + 0.01 * np.sin(300.0 * d)
+    return t
+
+
+def find_rotation_branch(t, point_time):
+    """findRotation (imageProjection.cpp:494-526) restated: which of its cases a point time takes."""
+    cur, imu_time = int(t["imu_pointer_cur"]), t["imu_time"]
+    front = 0
+    while front < cur:
+        if point_time < imu_time[front]:
+            break
+        front += 1
+    if point_time > imu_time[front] or front == 0:
+        return "before_first" if front == 0 else "past_last"
+    if point_time == imu_time[front]:
+        return "on_last"  # the loop ran out: interpolation with ratioFront = 1
+    return "on_sample" if point_time == imu_time[front - 1] else "between"
+
+
+def edge_times(n, cur, seed):
+    """Point times (float32, relative) that take every case of find_rotation."""
+    rng = np.random.default_rng(seed)
+    s = edge_sample_times(cur)
+    kind = rng.integers(0, 8, n)
+    out = rng.uniform(s[0], s[-1], n).astype(np.float32)                     # between samples
+    out = np.where(kind == 0, rng.uniform(-0.002, s[0], n).astype(np.float32), out)  # before the first
+    out = np.where((kind == 1) | (kind == 2), s[rng.integers(0, cur, n)], out)       # on a sample
+    out = np.where(kind == 3, s[-1], out)                                            # on the last
+    out = np.where(kind == 4, rng.uniform(s[-1], 0.11, n).astype(np.float32), out)   # past it
+    out[::97] = 0.0
+    return out.astype(np.float32)
+
+
+def _one_ring(pts):
+    pts = pts[pts["ring"] == 9].copy()
+    pts["ring"] = 0
+    return pts
+
+
+def edge_scan_variants(H, W, cur):
+    """The scan in firing order, shuffled, and with its first points rejected by each gate (ring out
+    of range, range < 1, NaN); intensity = input index.  In the last two the first point deskewPoint
+    sees is not input point 0 and, with more rings than one, not on ring 0."""
+    import proj_model as M
+    gt, _ = synth.job(17)
+    base = _one_ring(synth.scan(gt, 16, W, seed=17)) if H == 1 else synth.scan(gt, H, W, seed=17)
+    base["time"] = edge_times(len(base), cur, seed=H * 10000 + W + cur)
+
+    def first_late_ring(p, start):
+        kept, _, _ = M.keep_mask(p, H, W)
+        ok = kept & ((p["ring"] != 0) | (H == 1))
+        ok[:start] = False
+        return int(np.flatnonzero(ok)[0])
+
+    shuffled = base[np.random.default_rng(cur).permutation(len(base))].copy()
+    shuffled["ring"][:first_late_ring(shuffled, 1)] = 65535
+    lead = base.copy()
+    j = first_late_ring(lead, 3 * H + 5)
+    gate = np.arange(j) % 3
+    lead["ring"][:j][gate == 0] = H
+    for k in "xyz":
+        lead[k][:j][gate == 1] *= np.float32(0.01)
+    lead["x"][:j][gate == 2] = np.nan
+    out = {"in-order": base, "shuffled": shuffled, "leading-rejected": lead}
+    for p in out.values():
+        p["intensity"] = np.arange(len(p))
+    return out
+
+
+@pytest.mark.parametrize("H,W", EDGE_SHAPES)
+@pytest.mark.parametrize("name", list(EDGE_TABLES))
+def test_edge_scans_take_every_branch_of_find_rotation(H, W, name):
+    cur = EDGE_TABLES[name]
+    t = edge_table(cur)
+    P = default_params(H, W)
+    for variant, pts in edge_scan_variants(H, W, cur).items():
+        o = O.project(P, pts, deskew=t)
+        own = o["cloud"]["intensity"].astype(np.int64)  # the kept points: those deskewPoint sees
+        times = EDGE_TCUR + pts["time"][own[::4]].astype(np.float64)  # a quarter of them will do
+        taken = [find_rotation_branch(t, x) for x in times.tolist()]
+        for b in BRANCHES:
+            assert taken.count(b) > 0, (variant, b)
+        on = {x for x, b in zip(times.tolist(), taken) if b == "on_sample"}
+        assert len(on) >= min(cur, 3), variant  # exactly on several samples
+        assert np.abs(np.stack([o["cloud"][k] for k in "xyz"]) -
+                      np.stack([O.project(P, pts)["cloud"][k] for k in "xyz"])).max() > 1e-3  # and it moves points
+        if variant != "in-order":
+            first = int(own.min())
+            assert first > 0 and (H == 1 or pts["ring"][first] != 0), (variant, first)
+            assert variant == "shuffled" or first >= 3 * H + 5  # deep in the input
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", EDGE_SHAPES)
+def test_deskew_device_matches_oracle_at_find_rotation_edges(H, W):
+    P = default_params(H, W)
+    with api.Context(P) as ctx:
+        for name, cur in EDGE_TABLES.items():
+            t = edge_table(cur)
+            ctx.set_deskew([t])
+            for variant, pts in edge_scan_variants(H, W, cur).items():
+                g, o = ctx.project(pts), O.project(P, pts, deskew=t)
+                for k in ["start_ring", "end_ring", "col_ind", "range", "cloud"]:
+                    assert np.array_equal(np.ascontiguousarray(g[k]).view(np.uint8),
+                                          np.ascontiguousarray(o[k]).view(np.uint8)), (name, variant, k)

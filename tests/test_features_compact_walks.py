@@ -188,6 +188,12 @@ def _codes(paths):
     return corner, surf
 
 
+def _walk_words(ctx):
+    """The path record's words without bits 30..31, which name the k_features instance that ran
+    (tests/test_frontend_shapes.py checks those): the walks are compared across instances here."""
+    return (ctx.feature_paths() & np.uint32(0x3FFFFFFF)).tobytes()
+
+
 def _batch_bytes(cfg, scans, paths=False):
     """Poses + stats bytes of a default batch launch of `scans` against the config's map; with
     `paths` the path record's words behind them."""
@@ -196,7 +202,7 @@ def _batch_bytes(cfg, scans, paths=False):
         if paths:
             ctx.feature_paths()  # arm the record
         p, s = ctx.process_batch(scans, np.zeros((len(scans), 6), np.float32))
-        rec = ctx.feature_paths().tobytes() if paths else b""
+        rec = _walk_words(ctx) if paths else b""
     return p.tobytes() + s.tobytes() + rec
 
 
@@ -213,7 +219,7 @@ def _stream_bytes(scans, paths=False):
             pose, st = ctx.process_scan(pts, 0.2 * k, pose)
             out += pose.tobytes() + np.array([st[f] for f in sorted(st)], np.float64).tobytes()
             if paths:
-                out += ctx.feature_paths().tobytes()
+                out += _walk_words(ctx)
         f = ctx.extract_features(len(ctx.project(scans[-1])["col_ind"]))
         out += f["label"].tobytes() + f["corner"].tobytes() + f["surf"].tobytes()
     return out
