@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from .fbr_types import (DESKEW_TABLE, IMU_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
+from .fbr_types import (DESKEW_TABLE, GUESS_STATE, IMU_SAMPLE, MOTION, ODOM_INFO, ODOM_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
                         FbrGmapResult, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
                         POSE_SCORE, PointCloud2, default_params, gmap_params, icp_params, loop_params,
                         pg_marginal_params, pg_params, pose_lattice, ptr, sc_params, score_params)
@@ -35,7 +35,8 @@ EXPORTED_SYMBOLS = [
     "fbr_voxel_grid", "fbr_affine_from_pose", "fbr_pose_from_affine", "fbr_selftest_math", "fbr_selftest_eigen6", "fbr_selftest_gn_rows", "fbr_selftest_gn_reduce", "fbr_selftest_solve6", "fbr_selftest_eig_certified", "fbr_selftest_voxel_order", "fbr_selftest_radix_sort",
     "fbr_load_map", "fbr_pcd_read", "fbr_pcd_write_ascii", "fbr_pcd_write_binary",
     "fbr_msg_to_points", "fbr_points_to_msg_data", "fbr_project_msg", "fbr_process_msg",
-    "fbr_imu_convert", "fbr_imu_deskew_info", "fbr_set_deskew", "fbr_stream_copy_bandwidth", "fbr_valu_peak",
+    "fbr_imu_convert", "fbr_imu_deskew_info", "fbr_set_deskew", "fbr_odom_deskew_info", "fbr_motion_from_poses", "fbr_update_initial_guess", "fbr_set_motion",
+    "fbr_stream_copy_bandwidth", "fbr_valu_peak",
     "fbr_keyframe_params_default", "fbr_keyframes_add", "fbr_keyframes_set_pose", "fbr_keyframes_count",
     "fbr_keyframes_reset", "fbr_extract_surrounding_keyframes",
     "fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align", "fbr_selftest_nn1",
@@ -127,6 +128,10 @@ def lib():
             "fbr_imu_convert": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_imu_deskew_info": (ctypes.c_int, [_VP, _I64, ctypes.c_double, ctypes.c_double, _VP, _VP]),
             "fbr_set_deskew": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
+            "fbr_odom_deskew_info": (ctypes.c_int, [_VP, _I64, ctypes.c_double, ctypes.c_double, _VP, _VP]),
+            "fbr_motion_from_poses": (ctypes.c_int, [_VP, _VP, ctypes.c_double, ctypes.c_double, ctypes.c_double, _VP, _VP]),
+            "fbr_update_initial_guess": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP]),
+            "fbr_set_motion": (ctypes.c_int, [_VP, _VP, ctypes.c_int]),
             "fbr_stream_copy_bandwidth": (ctypes.c_int, [ctypes.c_int, _I64, ctypes.c_int, _VP]),
             "fbr_valu_peak": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _VP, _VP]),
             "fbr_keyframe_params_default": (None, [_VP]),
@@ -452,6 +457,47 @@ def imu_deskew_info(queue, time_scan_cur, time_scan_next, previous=None):
     return tab[0], n_pop.value
 
 
+def odom_deskew_info(queue, time_scan_cur, time_scan_next):
+    """odomDeskewInfo (imageProjection.cpp:395-491) on a queue of ODOM_SAMPLE records in arrival
+    order.  Returns (ODOM_INFO record, number of leading samples popped).  The record's motion has
+    flags 0: set FBR_MOTION_* (and the time source) before Context.set_motion."""
+    queue = _as_points(np.atleast_1d(queue), ODOM_SAMPLE)
+    info = np.zeros(1, ODOM_INFO)
+    n_pop = _I64()
+    _check(lib().fbr_odom_deskew_info(ptr(queue) if len(queue) else None, len(queue), ctypes.c_double(time_scan_cur),
+                                      ctypes.c_double(time_scan_next), ptr(info), ctypes.byref(n_pop)),
+           "fbr_odom_deskew_info")
+    return info[0], n_pop.value
+
+
+def motion_from_poses(prev, cur, dt, scan_period, dt_next):
+    """Constant velocity from two registered poses {roll, pitch, yaw, x, y, z} taken dt apart.
+    Returns (MOTION record for a scan of scan_period, the guess dt_next after `cur`)."""
+    prev = np.ascontiguousarray(prev, np.float32).reshape(6)
+    cur = np.ascontiguousarray(cur, np.float32).reshape(6)
+    m = np.zeros(1, MOTION)
+    guess = np.zeros(6, np.float32)
+    _check(lib().fbr_motion_from_poses(ptr(prev), ptr(cur), ctypes.c_double(dt), ctypes.c_double(scan_period),
+                                       ctypes.c_double(dt_next), ptr(m), ptr(guess)), "fbr_motion_from_poses")
+    return m[0], guess
+
+
+def update_initial_guess(state, odom, table, have_keyframes, use_imu_heading, pose):
+    """updateInitialGuess (mapOptmization.h:799-855).  state: a GUESS_STATE array of one record,
+    updated in place (None starts one); odom: ODOM_INFO record or None; table: DESKEW_TABLE record
+    or None.  Returns (pose, state)."""
+    st = np.zeros(1, GUESS_STATE) if state is None else state
+    if st.dtype != GUESS_STATE or st.shape != (1,):
+        raise TypeError("state: a GUESS_STATE array of one record")
+    od = None if odom is None else np.array(odom, ODOM_INFO).reshape(1)
+    tb = None if table is None else np.array(table, DESKEW_TABLE).reshape(1)
+    p = np.array(pose, np.float32).reshape(6).copy()
+    _check(lib().fbr_update_initial_guess(ptr(st), None if od is None else ptr(od), None if tb is None else ptr(tb),
+                                          int(bool(have_keyframes)), int(bool(use_imu_heading)), ptr(p)),
+           "fbr_update_initial_guess")
+    return p, st
+
+
 def _as_points(a, dtype):
     a = np.ascontiguousarray(a)
     if a.dtype != dtype:
@@ -580,6 +626,15 @@ class Context:
         _check(lib().fbr_process_msg(self._h, ctypes.byref(msg.c), ctypes.c_double(stamp), ptr(pose),
                                      ctypes.byref(st), ctypes.byref(fl)), "fbr_process_msg")
         return pose, st.as_dict(), fl.value
+
+    def set_motion(self, motions):
+        """Motion records (MOTION) for the following calls: job j of a batch uses motions[j], the
+        single-scan calls motions[0]; None turns the motion deskew off."""
+        if motions is None:
+            _check(lib().fbr_set_motion(self._h, None, 0), "fbr_set_motion")
+            return
+        m = np.ascontiguousarray(np.array(motions, MOTION).reshape(-1))
+        _check(lib().fbr_set_motion(self._h, ptr(m), len(m)), "fbr_set_motion")
 
     def set_deskew(self, tables):
         """IMU deskew tables (DESKEW_TABLE records) for the following calls: job j of a batch uses

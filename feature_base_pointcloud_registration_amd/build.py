@@ -23,7 +23,7 @@ HIP_SOURCES = ["k_project.hip", "k_features.hip", "k_voxel.hip", "k_voxel_ring.h
                "k_icp.hip", "k_scancontext.hip", "k_posegraph.hip", "k_pg_marginals.hip", "k_pg_direct.hip", "k_gmap.hip", "k_score.hip", "k_selftest.hip", "fbr_api.hip", "fbr_stages.hip",
                "fbr_scan.hip", "fbr_batch.hip", "fbr_comm.hip", "fbr_map.hip", "fbr_loop.hip", "fbr_sc.hip", "fbr_pg.hip",
                "fbr_gmap.hip", "fbr_score.hip"]
-HOST_SOURCES = ["fbr_pcd.cpp", "fbr_msg.cpp", "fbr_imu.cpp"]  # host-only C++ in the same library (PCD, PointCloud2, IMU)
+HOST_SOURCES = ["fbr_pcd.cpp", "fbr_msg.cpp", "fbr_imu.cpp", "fbr_odom.cpp"]  # host-only C++ in the same library (PCD, PointCloud2, IMU, odometry / motion)
 ARCH = os.environ.get("FBR_OFFLOAD_ARCH", "gfx950")
 
 

@@ -25,6 +25,16 @@ int drop_staged_batch(fbr_ctx* c) {
 }  // namespace internal
 }  // namespace fbr
 
+namespace {
+// d_desk_mode = the IMU bits of fbr_set_deskew | the motion bits of fbr_set_motion
+hipError_t upload_desk_modes(fbr_ctx* c) {
+  std::vector<int32_t> mode(c->Bcap, 0);
+  for (int j = 0; j < c->Bcap; ++j)
+    mode[j] = (j < (int)c->imu_mode.size() ? c->imu_mode[j] : 0) | (j < (int)c->mot_mode.size() ? c->mot_mode[j] : 0);
+  return fbr_memcpy_sync(c->d_desk_mode, mode.data(), sizeof(int32_t) * c->Bcap, hipMemcpyHostToDevice);
+}
+}  // namespace
+
 extern "C" {
 
 int fbr_batch_stage(fbr_ctx* c, const fbr_point_xyzirt* const* scans, const int64_t* n_in, int n_jobs,
@@ -46,8 +56,9 @@ int fbr_batch_stage(fbr_ctx* c, const fbr_point_xyzirt* const* scans, const int6
   };
   // Without deskew tables the scans go over as 16-B device records (x, y, z, ring bits; packed by
   // host threads, as fbr_process_batch's compact records are); a deskewing batch keeps the 24-B
-  // scans, whose time deskewPoint reads.
-  const bool pk = knobs::packed_scans() && !c->desk_any;
+  // scans, whose time deskewPoint reads (IMU tables and field-timed motions; a column-timed motion
+  // reads no time and keeps the records).
+  const bool pk = knobs::packed_scans() && !c->desk_any && !c->mot_field_any;
   if (pk) {
     if (!c->d_pk && dalloc(c->d_pk, (int64_t)c->Bcap * c->NMAX)) return FBR_ERR_HIP;
     std::vector<float4> rec;
@@ -119,8 +130,39 @@ int fbr_set_deskew(fbr_ctx* c, const fbr_deskew_table* tables, int n_tables) {
   if (any && !c->d_desk && dalloc(c->d_desk, c->Bcap)) return FBR_ERR_HIP;
   CK(fbr_sync(c->stream));
   if (any) CK(fbr_memcpy_sync(c->d_desk, tables, sizeof(fbr_deskew_table) * n_tables, hipMemcpyHostToDevice));
-  CK(fbr_memcpy_sync(c->d_desk_mode, mode.data(), sizeof(int32_t) * c->Bcap, hipMemcpyHostToDevice));
+  c->imu_mode = mode;
+  CK(upload_desk_modes(c));
   c->desk_any = any;
+  return FBR_OK;
+}
+
+int fbr_set_motion(fbr_ctx* c, const fbr_motion* motions, int n) {
+  if (!c || n < 0 || (n > 0 && !motions)) return FBR_ERR_INVALID_ARG;
+  if (n > c->Bcap) return FBR_ERR_CAPACITY;
+  CK(enter(c));
+  std::vector<int32_t> mode(c->Bcap, 0);
+  bool field = false, col = false;
+  for (int j = 0; j < n; ++j) {
+    const fbr_motion& m = motions[j];
+    if (!m.flags) continue;  // the job is untouched, whatever else the record holds
+    if (m.flags & ~(FBR_MOTION_POSITION | FBR_MOTION_ROTATION)) return FBR_ERR_INVALID_ARG;
+    if (m.time_source != FBR_TIME_FIELD && m.time_source != FBR_TIME_COLUMN) return FBR_ERR_INVALID_ARG;
+    if (m.time_source == FBR_TIME_COLUMN && m.column_direction != 1 && m.column_direction != -1)
+      return FBR_ERR_INVALID_ARG;
+    if (m.time_source == FBR_TIME_FIELD && !(m.scan_period > 0.0 && std::isfinite(m.scan_period)))
+      return FBR_ERR_INVALID_ARG;
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(m.incre[k])) return FBR_ERR_INVALID_ARG;
+    mode[j] = motion_mode_bits(m);
+    (m.time_source == FBR_TIME_COLUMN ? col : field) = true;
+  }
+  if ((field || col) && !c->d_motion && dalloc(c->d_motion, c->Bcap)) return FBR_ERR_HIP;
+  CK(fbr_sync(c->stream));
+  if (field || col) CK(fbr_memcpy_sync(c->d_motion, motions, sizeof(fbr_motion) * n, hipMemcpyHostToDevice));
+  c->mot_mode = mode;
+  CK(upload_desk_modes(c));
+  c->mot_field_any = field;
+  c->mot_col_any = col;
   return FBR_OK;
 }
 
@@ -129,7 +171,7 @@ int fbr_batch_launch(fbr_ctx* c) {
   if (c->staged_B <= 0) return FBR_ERR_STATE;
   if (!c->has_map) return FBR_ERR_NO_MAP;
   // deskew tables set after the batch was staged as 16-B records (no time field): stage it again
-  if (c->desk_any && !c->no_time_call && !c->staged_24) return FBR_ERR_STATE;
+  if ((c->desk_any || c->mot_field_any) && !c->no_time_call && !c->staged_24) return FBR_ERR_STATE;
   CK(enter(c));
   const auto t0 = std::chrono::steady_clock::now();
   // Sub-batches on separate streams: one sub-batch's low-occupancy phases (the features' ring-0
@@ -369,7 +411,7 @@ int ingest_upload(fbr_ctx* c, int slot, const fbr_point_xyzirt* const* scans, co
   Ingest& g = c->ing;
   fbr_point_xyzirt* dst = g.d_pts_slot[slot];
   // compact records unless a deskew table may read the per-point time (deskewPoint, :545-580)
-  const bool compact = knobs::ingest_compact() && !c->desk_any;
+  const bool compact = knobs::ingest_compact() && !c->desk_any && !c->mot_field_any;
   g.compact_used = compact;
   // compact records expand into 16-B device records (k_project / k_compact read those)
   const bool pk = compact && knobs::packed_scans();

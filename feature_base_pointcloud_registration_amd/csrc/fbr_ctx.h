@@ -43,6 +43,7 @@
 #include "fbr_common.h"
 #include "fbr_imu.h"
 #include "fbr_kernels.h"
+#include "fbr_motion.h"
 #include "fbr_knobs.h"
 #include "fbr_msg.h"
 #include "fbr_own.h"
@@ -342,8 +343,13 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   Dev<int32_t> d_desk_mode;      // [Bcap] kDesk* bits per job
   Dev<int32_t> d_rowmin;         // [Bcap][H] minimum owner per row
   Dev<int32_t> d_choff;          // [Bcap][H][W / 32 + 1] compaction tile offsets
-  bool desk_any = false;         // some job has a non-zero mode
+  bool desk_any = false;         // some job has an IMU mode (kDeskPoints | kDeskImu)
   bool no_time_call = false;     // the current call's PointCloud2 has no "time" field
+  // Motion deskew (fbr_set_motion, fbr_batch.hip): d_desk_mode holds both setters' bits
+  Dev<fbr_motion> d_motion;               // [Bcap] records (allocated on first use)
+  std::vector<int32_t> imu_mode, mot_mode;  // [Bcap] each setter's bits (empty: none set yet)
+  bool mot_field_any = false;    // some job's motion takes its time from the field (needs the 24-B scans)
+  bool mot_col_any = false;      // some job's motion takes its time from the column
 
   // ---- Gauss-Newton work arrays, run driver state and results (fbr_stages.hip) ----
   Dev<GnState> d_gn;

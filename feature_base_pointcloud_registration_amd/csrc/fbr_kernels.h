@@ -78,7 +78,8 @@ inline int64_t ingest_region_bytes(int64_t nmax) { return (14 * nmax + 48 + 15) 
 // Batch scans may live on the device as 16-B records (ScanRec): float4 (x, y, z, ring as int bits
 // in w), one dwordx4 per point where the 24-B fbr_point_xyzirt costs 24 B of cache lines for the 16
 // projection and extraction read.  pk = the records (null: the 24-B scans); intensity and time are
-// not carried, so launches that deskew keep the 24-B scans.
+// not carried, so launches whose deskew reads a point's time (an IMU table, a field-timed motion)
+// keep the 24-B scans; column-timed motions read no time and keep the records.
 // out: fbr_point_xyzirt records, or with pk the 16-B ones.
 void launch_expand_scans(hipStream_t s, const uint8_t* stage, int64_t nmax, int B, const int64_t* nin,
                          const int64_t* off, int rb, void* out, bool pk);
@@ -100,10 +101,18 @@ void launch_project(hipStream_t s, const fbr_point_xyzirt* pts, const int64_t* n
 // Optional IMU deskew of the kept points (deskewPoint, imageProjection.cpp:545-580): desk_mode
 // [B] (kDesk* bits, fbr_imu.h) and desk [B] tables, both null when no job deskews; rowmin [B][H]
 // receives each row's minimum owner (the scan's first deskewed point is the minimum over rows).
+// Motion deskew (fbr_set_motion, fbr_motion.h): motion [B] records, read for jobs whose mode has a
+// kDeskMot* bit.  no_time: the call's cloud has no `time` field, so the IMU rotation and a
+// field-timed motion are off for it and only column-timed motions apply.  col_motion: no job of the
+// launch reads `time` (column-timed motions only), so 16-B record launches take the per-tile
+// transform table instances of k_compact.
 struct DeskArgs {
   const int32_t* mode;
   const fbr_deskew_table* table;
   int32_t* rowmin;
+  const fbr_motion* motion = nullptr;
+  int no_time = 0;
+  int col_motion = 0;
 };
 // The 12-B cloud record of the batch front end (x, y, z; 4-B aligned), beside float4 in the same
 // allocation: a job's records start at its float4 base (cloud + job * HW) and are packed 12 B apart.

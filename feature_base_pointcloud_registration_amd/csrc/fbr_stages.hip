@@ -254,24 +254,34 @@ static VgRing ring_filter_choice(fbr_ctx* c, const Sub& sb) {
   return v;
 }
 
+// Whether the call's extraction reads the points' `time`: an IMU table or a field-timed motion on
+// some job, and a cloud that has the field.  Such launches need the 24-B scans.
+static bool reads_point_time(const fbr_ctx* c) { return (c->desk_any || c->mot_field_any) && !c->no_time_call; }
+
 // Whether a sub-batch's projected cloud is Pt3 records (fbr_kernels.h).  Only where every reader of
-// the launch takes them and the fourth word is the constant 0: 16-B scan records (so no deskew, no
-// intensity), not stream mode (fbr_project / fbr_extract_features hand the float4 cloud out), and
+// the launch takes them and the fourth word is the constant 0: 16-B scan records (so no deskew that reads a
+// point's time, no intensity), not stream mode (fbr_project / fbr_extract_features hand the float4 cloud out), and
 // the four-wave per-ring filter (the exact-order and 512-thread kernels read float4).  stage_project
 // and stage_features of one launch both decide by this, from state that does not change between them.
 static bool batch_cloud12(fbr_ctx* c, const Sub& sb) {
   if (sb.stream_mode || c->diag_wide_cloud) return false;
-  if ((c->desk_any && !c->no_time_call) || !c->staged_pk) return false;  // (stage_project's pk)
+  if (reads_point_time(c) || !c->staged_pk) return false;  // (stage_project's pk)
   return vr_takes_four_waves(ring_filter_choice(c, sb));
 }
 
 int stage_project(fbr_ctx* c, const Sub& sb) {
   const int64_t j0 = sb.j0, i0 = sb.in0;
   DeskArgs desk{nullptr, nullptr, nullptr};
-  if (c->desk_any && !c->no_time_call)  // deskewFlag == -1 without a "time" field (:296-297, :548)
-    desk = DeskArgs{c->d_desk_mode + i0, c->d_desk + i0, c->d_rowmin + j0 * c->H};
-  // batch jobs read the 16-B device records when the staged batch has them and nothing deskews
-  const float4* pk = (!sb.stream_mode && !desk.mode && c->staged_pk) ? c->staged_pk + i0 * c->NMAX : nullptr;
+  const bool timed = reads_point_time(c);
+  if (timed || c->mot_col_any) {  // deskewFlag == -1 without a "time" field (:296-297, :548)
+    desk = DeskArgs{c->d_desk_mode + i0, c->d_desk ? c->d_desk + i0 : nullptr, c->d_rowmin + j0 * c->H};
+    desk.motion = c->d_motion ? c->d_motion + i0 : nullptr;
+    desk.no_time = c->no_time_call ? 1 : 0;
+    desk.col_motion = timed ? 0 : 1;
+  }
+  // batch jobs read the 16-B device records when the staged batch has them and nothing reads a
+  // point's time (no deskew, or column-timed motions only)
+  const float4* pk = (!sb.stream_mode && !timed && c->staged_pk) ? c->staged_pk + i0 * c->NMAX : nullptr;
   if (!sb.stream_mode && !pk && !c->staged_24) return FBR_ERR_STATE;  // deskew tables set after a 16-B upload
   int32_t* owner = c->d_owner + j0 * c->HW;
   OwnerTag ot;

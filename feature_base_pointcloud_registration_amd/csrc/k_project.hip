@@ -16,6 +16,10 @@
 //                 written before deskewPoint, :633-635), and transStartInverse comes from the first
 //                 point deskewPoint sees, which is the minimum owner of the scan (the first point
 //                 in input order that passes every check always wins its cell).
+//                 With a motion record (fbr_set_motion, fbr_motion.h) deskewPoint also runs
+//                 findPosition's commented body (:528-542), the time of a point from its `time`
+//                 field or from its column; column-timed motions alone run on the 16-B records
+//                 through a per-tile table of column transforms (k_compact's kMot instances).
 // Roofline: HBM-bound.  Algorithmic bytes: 24 B per raw point read (K1), 4 B/cell owner
 // write+read, 24 B per valid point written (xyzi 16 + col 4 + range 4).
 #include <algorithm>
@@ -26,6 +30,7 @@
 #include "fbr_imu.h"
 #include "fbr_kernels.h"
 #include "fbr_knobs.h"
+#include "fbr_motion.h"
 
 namespace fbr {
 
@@ -225,6 +230,32 @@ __device__ __forceinline__ float4 deskew_point(const fbr_point_xyzirt& q, const 
   return make_float4(o[0], o[1], o[2], q.intensity);
 }
 
+// What a job's deskew does in this call (DeskArgs): the IMU rotation and a field-timed motion need
+// the cloud's `time` field, a column-timed motion does not.
+struct DeskJob {
+  bool imu;  // findRotation from the job's table
+  int mot;   // the job's kDeskMot* bits, 0 when its motion is off for this call
+};
+__device__ __forceinline__ DeskJob desk_job(const DeskArgs& desk, int job) {
+  const int mode = desk.mode[job];
+  DeskJob d;
+  d.imu = (mode & kDeskPoints) && !desk.no_time;
+  d.mot = (mode & kDeskMotion) && ((mode & kDeskMotCol) || !desk.no_time) ? (mode & (kDeskMotion | kDeskMotCol)) : 0;
+  return d;
+}
+
+// transFinal of one raw point of a job with a motion record (fbr_motion.h): findPosition live, the
+// rotation findRotation's with an IMU table and the increment's otherwise.  col: the point's column.
+__device__ __forceinline__ Aff3 motion_final(const fbr_point_xyzirt& q, int col, int col_first, int W, const DeskJob& d,
+                                             const fbr_deskew_table* T, const fbr_motion& M) {
+  float rot[3] = {0.0f, 0.0f, 0.0f}, pos[3];
+  if (d.imu) find_rotation(*T, T->time_scan_cur + (double)q.time, &rot[0], &rot[1], &rot[2]);
+  const float ratio = (d.mot & kDeskMotCol) ? motion_ratio_column(motion_column_k(M.column_direction, col, col_first, W), W)
+                                            : motion_ratio_field(q.time, M.scan_period);
+  motion_pos_rot(M.incre, d.mot, ratio, d.imu, rot, pos);
+  return motion_trans_final(rot, pos);
+}
+
 // One workgroup per (job, HB-row block, CG-column chunk) tile.  The owner tile is read row by row
 // (coalesced), the owning raw points are gathered column by column (in the sensor's firing order
 // consecutive rings of one column are consecutive raw points, so a wave's gather is one contiguous
@@ -236,7 +267,13 @@ __device__ __forceinline__ float4 deskew_point(const fbr_point_xyzirt& q, const 
 // from it at the write, same expression, same bits): 20 KB per 1024-cell tile.
 // k12 (kPk launches whose readers take Pt3, fbr_kernels.h): the cloud is written as 12-B records, three
 // dwords at rowoff + rank from the job's float4 base; col and range as in every other instance.
-template <bool kDesk, bool kPk = false, bool k12 = false>
+// kMot (kPk launches whose deskew is column-timed motions only, DeskArgs::col_motion): transBt of a
+// point depends on its column alone, so a tile has at most CG distinct transforms.  One lane per
+// tile column computes its column's (from col_first, the column of the scan's minimum owner, and the
+// job's 48-B record) into LDS, 12 floats per column as [12][CG] (consecutive lanes on consecutive
+// banks); the write applies them to the staged raw point: 9 products and 9 sums per point, and the
+// range is still the raw point's.  The gather loop is the no-motion one.
+template <bool kDesk, bool kPk = false, bool k12 = false, bool kMot = false>
 __global__ void __launch_bounds__(256)
 k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ pk, int64_t nmax, int32_t* __restrict__ owner,
           const int32_t* __restrict__ rowcnt, const int32_t* __restrict__ choff, int B, int H, int W, int HB, int CG,
@@ -251,6 +288,7 @@ k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ p
   float4* pxyz = lds_c;                                    // [HB][PC] gathered xyzi
   int32_t* own = reinterpret_cast<int32_t*>(pxyz + HB * PC);  // [HB][PC] owners of the tile
   float* prng = reinterpret_cast<float*>(own + HB * PC);   // [HB][PC] range (deskew only)
+  float* mtab = prng;                                      // [12][CG] column transforms (kMot only)
   __shared__ int32_t rowoff[64];    // output offset of each tile row before this chunk
   __shared__ int32_t scan[256];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -329,17 +367,55 @@ k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ p
   }
   // deskew: transStartInverse from the scan's first deskewed point (the minimum owner)
   const fbr_point_xyzirt* P = pts + (int64_t)job * nmax;
-  const bool dsk = kDesk && (desk.mode[job] & kDeskPoints);
-  const fbr_deskew_table* DT = dsk ? desk.table + job : nullptr;
+  DeskJob dj{false, 0};
+  if constexpr (kDesk) dj = desk_job(desk, job);
+  const bool dsk = kDesk && (dj.imu || dj.mot);
+  const fbr_deskew_table* DT = dj.imu ? desk.table + job : nullptr;
   Rot3 Ls;
   float ts[3] = {0.0f, 0.0f, 0.0f};
+  int col_first = 0;
   if (dsk) {
     int mn = kEmptyOwner;
     for (int r = lane; r < H; r += 64) mn = min(mn, desk.rowmin[job * H + r]);
     for (int s = 32; s > 0; s >>= 1) mn = min(mn, __shfl_xor(mn, s));
-    float rx = 0.0f, ry = 0.0f, rz = 0.0f;
-    if (mn != kEmptyOwner) find_rotation(*DT, DT->time_scan_cur + (double)P[mn].time, &rx, &ry, &rz);
-    affine_inverse(rot_rpy(rx, ry, rz), Ls, ts);
+    if (!dj.mot) {
+      float rx = 0.0f, ry = 0.0f, rz = 0.0f;
+      if (mn != kEmptyOwner) find_rotation(*DT, DT->time_scan_cur + (double)P[mn].time, &rx, &ry, &rz);
+      affine_inverse(rot_rpy(rx, ry, rz), Ls, ts);
+    } else if (mn != kEmptyOwner) {
+      const fbr_point_xyzirt q = P[mn];
+      int row;
+      if (dj.mot & kDeskMotCol) project_point(q, H, W, row, col_first);  // the minimum owner passed k_project
+      const Aff3 f = motion_final(q, col_first, col_first, W, dj, DT, desk.motion[job]);
+      affine_inverse_t(f.r, f.t, Ls, ts);
+    }
+  }
+  // kMot: the tile's column transforms, while the other waves gather
+  int mot = 0;
+  if constexpr (kMot) {
+    const int mode = desk.mode[job];
+    mot = (mode & kDeskMotCol) ? (mode & kDeskMotion) : 0;  // wave-uniform
+    if (mot && tid < ((CG + 63) & ~63)) {  // whole waves: the reduction below takes all 64 lanes
+      int mn = kEmptyOwner;
+      for (int r = lane; r < H; r += 64) mn = min(mn, desk.rowmin[job * H + r]);
+      for (int s = 32; s > 0; s >>= 1) mn = min(mn, __shfl_xor(mn, s));
+      if (tid < CG) {
+        int row, cf = 0;
+        if (mn != kEmptyOwner) {  // re-project the first kept record for its column (uniform over the lanes)
+          const float4 f = pk[(int64_t)job * nmax + mn];
+          project_xyzr(f.x, f.y, f.z, __float_as_int(f.w), H, W, row, cf);
+        }
+        const fbr_motion& M = desk.motion[job];
+        const float ratio = motion_ratio_column(motion_column_k(M.column_direction, c0 + tid, cf, W), W);
+        const Aff3 T = motion_transform(M.incre, mot, motion_ratio_column(0, W), ratio);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+          for (int j = 0; j < 3; ++j) mtab[(3 * i + j) * CG + tid] = T.r.m[i][j];
+          mtab[(9 + i) * CG + tid] = T.t[i];
+        }
+      }
+    }
   }
   // gather, column by column (consecutive threads = consecutive rings of one column)
   if (kDesk) {
@@ -348,7 +424,16 @@ k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ p
       const int32_t o = own[k];
       if (o != kEmptyOwner) {
         const fbr_point_xyzirt q = P[o];
-        pxyz[k] = dsk ? deskew_point(q, *DT, Ls, ts) : make_float4(q.x, q.y, q.z, q.intensity);
+        if (dsk && dj.mot) {  // transBt = transStartInverse * transFinal, with findPosition live
+          const Aff3 f = motion_final(q, c0 + c, col_first, W, dj, DT, desk.motion[job]);
+          Rot3 Rb;
+          float tb[3], o3[3];
+          compose_t(Ls, ts, f.r, f.t, Rb, tb);
+          apply_affine(Rb, tb, q.x, q.y, q.z, o3);
+          pxyz[k] = make_float4(o3[0], o3[1], o3[2], q.intensity);
+        } else {
+          pxyz[k] = dsk ? deskew_point(q, *DT, Ls, ts) : make_float4(q.x, q.y, q.z, q.intensity);
+        }
         prng[k] = sqrt_rn(q.x * q.x + q.y * q.y + q.z * q.z);
       }
     }
@@ -406,10 +491,28 @@ k_compact(const fbr_point_xyzirt* __restrict__ pts, const float4* __restrict__ p
     if (v) {
       const int dst = rowoff[r] + rank;
       const float4 p = pxyz[k];
-      if constexpr (k12) reinterpret_cast<Pt3*>(C)[dst] = Pt3{p.x, p.y, p.z};
-      else C[dst] = p;
+      if constexpr (kMot) {
+        float4 d = p;
+        if (mot) {  // the column's transBt on the staged raw point (deskewPoint, :574-576)
+          Rot3 Rb;
+          float tb[3], o3[3];
+#pragma unroll
+          for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) Rb.m[i][j] = mtab[(3 * i + j) * CG + c];
+            tb[i] = mtab[(9 + i) * CG + c];
+          }
+          apply_affine(Rb, tb, p.x, p.y, p.z, o3);
+          d = make_float4(o3[0], o3[1], o3[2], p.w);
+        }
+        if constexpr (k12) reinterpret_cast<Pt3*>(C)[dst] = Pt3{d.x, d.y, d.z};
+        else C[dst] = d;
+      } else {
+        if constexpr (k12) reinterpret_cast<Pt3*>(C)[dst] = Pt3{p.x, p.y, p.z};
+        else C[dst] = p;
+      }
       CI[dst] = c0 + c;
-      R[dst] = kDesk ? prng[k] : sqrt_rn(p.x * p.x + p.y * p.y + p.z * p.z);
+      R[dst] = kDesk ? prng[k] : sqrt_rn(p.x * p.x + p.y * p.y + p.z * p.z);  // the raw point's range
     }
   }
 }
@@ -528,13 +631,21 @@ void launch_extract(hipStream_t s, const fbr_point_xyzirt* pts, int64_t nmax, in
                     int32_t* start_ring, int32_t* end_ring, int32_t* nvalid, const DeskArgs& desk, const float4* pk,
                     const OwnerTag& ot, bool c12) {
   const CompactTile T = compact_tile(H, knobs::compact_cells());
+  const bool cmot = desk.mode && desk.col_motion && pk;  // column-timed motions on 16-B records
   fbr_launch(k_rowcount, dim3(H, B), dim3(64), 0, s, owner, H, W, T.cg, rowcnt, desk.mode ? desk.rowmin : nullptr,
              choff, ot);
   const int tiles = ((H + T.hb - 1) / T.hb) * compact_nchunk(T.cg, W);
   const int groups = (B + 7) / 8;
   const dim3 grid((unsigned)(groups * 8 * tiles));
   const size_t cells = (size_t)T.hb * (T.cg + 1);  // padded pitch (k_compact)
-  if (desk.mode)
+  const uint32_t lds_mot = (uint32_t)(cells * 20 + (size_t)T.cg * 48);  // + the [12][CG] transform table
+  if (cmot && c12)
+    fbr_launch((k_compact<false, true, true, true>), grid, dim3(256), lds_mot, s, pts, pk, nmax, owner, rowcnt, choff, B,
+               H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);
+  else if (cmot)
+    fbr_launch((k_compact<false, true, false, true>), grid, dim3(256), lds_mot, s, pts, pk, nmax, owner, rowcnt, choff, B,
+               H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);
+  else if (desk.mode)
     fbr_launch(k_compact<true>, grid, dim3(256), (uint32_t)(cells * 24), s, pts, pk, nmax, owner, rowcnt, choff, B,
                H, W, T.hb, T.cg, cloud, col, range, start_ring, end_ring, nvalid, desk, ot);
   else if (pk && c12)

@@ -34,6 +34,30 @@ DESKEW_TABLE = np.dtype([("status", "<i4"), ("imu_available", "<i4"), ("imu_poin
 assert DESKEW_TABLE.itemsize == 32 + 4 * 8 * IMU_QUEUE
 FBR_DESKEW_READY, FBR_DESKEW_WAIT_IMU = 0, 1
 
+# Motion deskew and the odometry guess (include/fbr.h "Motion deskew"): fbr_motion, fbr_odom_sample,
+# fbr_odom_info, fbr_guess_state
+FBR_MOTION_POSITION, FBR_MOTION_ROTATION = 1, 2
+FBR_TIME_FIELD, FBR_TIME_COLUMN = 0, 1
+MOTION = np.dtype([("flags", "<i4"), ("time_source", "<i4"), ("column_direction", "<i4"), ("reserved_", "<i4"),
+                   ("incre", "<f4", 6), ("scan_period", "<f8")], align=True)
+assert MOTION.itemsize == 48
+ODOM_SAMPLE = np.dtype([("stamp", "<f8"), ("position", "<f8", 3), ("orientation", "<f8", 4), ("covariance0", "<f8")])
+assert ODOM_SAMPLE.itemsize == 72
+ODOM_INFO = np.dtype([("odom_available", "<i4"), ("odom_deskew_flag", "<i4"), ("initial_guess", "<f4", 6),
+                      ("reset_id", "<i4"), ("reserved_", "<i4"), ("motion", MOTION)], align=True)
+assert ODOM_INFO.itemsize == 88
+GUESS_STATE = np.dtype([("reset_id", "<i4"), ("reserved_", "<i4"), ("last_imu", "<f4", 12)])
+assert GUESS_STATE.itemsize == 56
+
+
+def motion(incre, flags=FBR_MOTION_POSITION | FBR_MOTION_ROTATION, time_source=FBR_TIME_FIELD, scan_period=0.1,
+           column_direction=1):
+    """One MOTION record: incre = (rollIncre, pitchIncre, yawIncre, x, y, z) of the scan."""
+    m = np.zeros(1, MOTION)
+    m["flags"], m["time_source"], m["column_direction"] = flags, time_source, column_direction
+    m["incre"], m["scan_period"] = np.asarray(incre, np.float32), scan_period
+    return m[0]
+
 # LIO-SAM keyframe store (include/fbr.h "LIO-SAM keyframe local map")
 KEYPOSE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("roll", "<f4"),
                     ("pitch", "<f4"), ("yaw", "<f4"), ("pad_", "<f4"), ("time", "<f8")])

@@ -213,7 +213,8 @@ int fbr_process_msg(fbr_ctx* ctx, const fbr_pointcloud2* msg, double stamp, floa
  *                        imuRollInit / imuPitchInit.
  * findPosition is all-zero in the reference (:528-542, positional deskew commented out), and the
  * odometry half of deskewInfo only fills initial-guess fields read by the disabled
- * updateInitialGuess; neither has an observable effect on this path. */
+ * updateInitialGuess; neither has an observable effect on this path while it stays off.  The
+ * motion entry points below (fbr_set_motion and its companions) switch both on. */
 #define FBR_IMU_QUEUE 500 /* queueLength, imageProjection.cpp:23 */
 
 typedef struct fbr_imu_sample { /* the sensor_msgs/Imu fields the path reads */
@@ -261,6 +262,96 @@ int fbr_imu_deskew_info(const fbr_imu_sample* imu_queue, int64_t n_imu, double t
  * runtime behaviour (no deskew, imuAvailable = 0).  A PointCloud2 without a "time" field disables
  * the point deskew for that call (deskewFlag = -1, :296-297, :548) but not the IMU update. */
 int fbr_set_deskew(fbr_ctx* ctx, const fbr_deskew_table* tables, int n_tables);
+
+/* ---- Motion deskew from odometry or the pose chain, and the odometry guess -------------------
+ * The rest of LIO-SAM's motion path, which the reference carries switched off:
+ *   fbr_odom_deskew_info     odomDeskewInfo (imageProjection.cpp:395-491): the initial-guess fields,
+ *                            odomAvailable, and the scan's begin-to-end increment of
+ *                            transBegin^-1 * transEnd as a fbr_motion
+ *   fbr_motion_from_poses    the same record from the last two registration results (constant
+ *                            velocity), for hosts without odometry, with the predicted next guess
+ *   fbr_update_initial_guess updateInitialGuess (mapOptmization.h:799-855) on a caller-owned state
+ *   fbr_set_motion           hands fbr_motion records to the device: deskewPoint (:545-580) then runs
+ *                            with findPosition's commented body live (:528-542)
+ * The arithmetic of one point (csrc/fbr_motion.h, the same code on the host and in the kernels):
+ *   ratio   FBR_TIME_FIELD:  (float)((double)point.time / scan_period)
+ *           FBR_TIME_COLUMN: (float)k / (float)W, k = (column_direction * (col - col_first)) mod W
+ *                            in [0, W), col the kept cell's column, col_first the column of the
+ *                            scan's first kept point in input order (a spinning sensor sweeps its
+ *                            columns at a constant rate, as LOAM / LeGO-LOAM take it)
+ *   pos     ratio * incre[3..5] with FBR_MOTION_POSITION, else 0
+ *   rot     findRotation's when the job has an IMU table with imu_available (fbr_set_deskew; it
+ *           reads the point's time whatever time_source says); else ratio * incre[0..2] with
+ *           FBR_MOTION_ROTATION; else 0
+ *   transFinal = getTransformation(pos, rot); transStartInverse = transFinal(first point).inverse()
+ *   (Eigen: t' = (-L^-1) * t); transBt = transStartInverse * transFinal (t = L1 * t2 + t1); float,
+ *   3-term sums as x0 + (x1 + x2), no FMA.
+ * Only the cloud changes (and the feature clouds taken from it): range, col_ind and start/end_ring
+ * stay the raw point's (rangeMat is written before deskewPoint, :633-635).  With FBR_TIME_COLUMN the
+ * transform depends on the column alone, so it needs neither the `time` field nor the 24-B scans: it
+ * runs on a batch's 16-B device records and on a PointCloud2 without "time", where the IMU deskew
+ * and FBR_TIME_FIELD are disabled (FBR_MSG_NO_TIME). */
+#define FBR_MOTION_POSITION 1 /* findPosition live                                               */
+#define FBR_MOTION_ROTATION 2 /* rotation from the increment when the job has no IMU table       */
+#define FBR_TIME_FIELD 0
+#define FBR_TIME_COLUMN 1
+typedef struct fbr_motion {
+  int32_t flags, time_source, column_direction /* +1 | -1, COLUMN only */, reserved_;
+  float incre[6];     /* rollIncre, pitchIncre, yawIncre, odomIncreX, Y, Z of transBegin^-1 * transEnd */
+  double scan_period; /* FIELD only; > 0 */
+} fbr_motion;         /* 48 bytes */
+
+typedef struct fbr_odom_sample { /* the nav_msgs/Odometry fields the path reads */
+  double stamp;                  /* header.stamp.toSec()      */
+  double position[3];            /* pose.pose.position        */
+  double orientation[4];         /* x, y, z, w                */
+  double covariance0;            /* pose.covariance[0]: the IMU pre-integration reset id */
+} fbr_odom_sample;               /* 72 bytes */
+
+typedef struct fbr_odom_info {
+  int32_t odom_available;   /* cloudInfo.odomAvailable                                       */
+  int32_t odom_deskew_flag; /* odomDeskewFlag                                                */
+  float initial_guess[6];   /* initialGuess{Roll, Pitch, Yaw, X, Y, Z}                       */
+  int32_t reset_id;         /* cloudInfo.imuPreintegrationResetId                            */
+  int32_t reserved_;
+  fbr_motion motion;        /* flags 0 unless odom_deskew_flag: the caller ORs in FBR_MOTION_* */
+} fbr_odom_info;            /* 88 bytes */
+
+typedef struct fbr_guess_state { /* what updateInitialGuess keeps between scans */
+  int32_t reset_id;              /* the mapping side's imuPreintegrationResetId (caller-owned) */
+  int32_t reserved_;
+  float last_imu[12];            /* lastImuTransformation, row-major 3x4 */
+} fbr_guess_state;               /* 56 bytes */
+
+/* odomDeskewInfo on a queue of samples in arrival order.  *n_pop receives the number of leading
+ * samples it pops (stamp < time_scan_cur - 0.01).  out->motion has time_source FBR_TIME_FIELD,
+ * column_direction +1, scan_period = time_scan_next - time_scan_cur and, when odom_deskew_flag is
+ * set, the increment; its flags are 0 (the reference runs with the path off): set
+ * FBR_MOTION_POSITION (| FBR_MOTION_ROTATION) and the time source before fbr_set_motion. */
+int fbr_odom_deskew_info(const fbr_odom_sample* odom_queue, int64_t n_odom, double time_scan_cur,
+                         double time_scan_next, fbr_odom_info* out, int64_t* n_pop);
+/* Constant velocity from two registered poses {roll, pitch, yaw, x, y, z} taken dt apart: the six
+ * components of prev^-1 * cur scaled by scan_period / dt are the increment (flags POSITION |
+ * ROTATION, FIELD time, direction +1), and scaled by dt_next / dt they predict the next scan's
+ * guess, guess_out = cur * getTransformation(...).  out or guess_out may be NULL.
+ * FBR_ERR_INVALID_ARG for dt <= 0 or a non-finite input. */
+int fbr_motion_from_poses(const float prev[6], const float cur[6], double dt, double scan_period,
+                          double dt_next, fbr_motion* out, float guess_out[6]);
+/* updateInitialGuess on pose_inout (transformTobeMapped): the first frame (have_keyframes == 0)
+ * from the IMU attitude of `table`; the odometry guess while odom->odom_available and
+ * odom->reset_id == state->reset_id; else, with table->imu_available, the IMU rotation increment
+ * since the last call applied to the previous pose.  odom or table may be NULL (not available);
+ * with neither branch taken the pose is left as it is.  Touches no context. */
+int fbr_update_initial_guess(fbr_guess_state* state, const fbr_odom_info* odom, const fbr_deskew_table* table,
+                             int have_keyframes, int use_imu_heading, float pose_inout[6]);
+/* Motion records for the following calls, addressed as fbr_set_deskew's tables: job j of a staged
+ * batch uses motions[j] (j < n), the single-scan calls use motions[0]; NULL or n == 0 turns the
+ * path off.  A job with flags == 0 is untouched.  FBR_ERR_INVALID_ARG for unknown flags or
+ * time_source, a column_direction other than +1 / -1, scan_period <= 0 with FBR_TIME_FIELD, or a
+ * non-finite increment.  With FBR_TIME_FIELD a PointCloud2 without "time" disables the job's motion
+ * deskew for that call, and a batch staged as 16-B records answers FBR_ERR_STATE at launch (stage
+ * it again); with FBR_TIME_COLUMN neither applies.  fbr_reset_stream keeps the records. */
+int fbr_set_motion(fbr_ctx* ctx, const fbr_motion* motions, int n);
 
 /* ---- LIO-SAM keyframe local map ------------------------------------
  * The reference's mapping back-end (laserCloudInfoHandler, mapOptmization.h:346-389) registers
@@ -966,10 +1057,11 @@ int fbr_debug_counters(long long* launches, long long* host_syncs, long long* fl
  * n-1's last iterations.  The single-scan entry points (fbr_project, fbr_register*,
  * fbr_process_scan) share the device buffers and drop a staged batch (after enqueueing every
  * launch in flight): fbr_batch_launch then returns FBR_ERR_STATE until the next fbr_batch_stage.
- * Without deskew tables the staged scans live on the device as 16-B records (x, y, z, ring):
- * intensity and time reach no batch result (poses, statistics, feature masks) and are not copied;
- * a batch staged that way and then given deskew tables (fbr_set_deskew) is reported FBR_ERR_STATE
- * at launch (stage it again). */
+ * Without deskew tables and field-timed motions the staged scans live on the device as 16-B
+ * records (x, y, z, ring): intensity and time reach no batch result (poses, statistics, feature
+ * masks) and are not copied; a batch staged that way and then given deskew tables (fbr_set_deskew)
+ * or FBR_TIME_FIELD motions (fbr_set_motion) is reported FBR_ERR_STATE at launch (stage it again).
+ * FBR_TIME_COLUMN motions read no time and run on the records. */
 int fbr_batch_stage(fbr_ctx* ctx, const fbr_point_xyzirt* const* scans, const int64_t* n_in,
                     int n_jobs, const float* poses_in /* [n_jobs][6] */);
 int fbr_batch_launch(fbr_ctx* ctx);

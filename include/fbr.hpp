@@ -198,6 +198,30 @@ class ImageProjection {
   void setDeskew(const fbr_deskew_table& t) { check(fbr_set_deskew(c_.get(), &t, 1), "fbr_set_deskew"); }
   void clearDeskew() { check(fbr_set_deskew(c_.get(), nullptr, 0), "fbr_set_deskew"); }
 
+  /* The odometry half of deskewInfo() and findPosition's body enabled: the motion record of the
+   * next scan (from odomDeskewInfo or motionFromPoses, its FBR_MOTION_* flags set by the caller). */
+  void setMotion(const fbr_motion& m) { check(fbr_set_motion(c_.get(), &m, 1), "fbr_set_motion"); }
+  void clearMotion() { check(fbr_set_motion(c_.get(), nullptr, 0), "fbr_set_motion"); }
+  /* odomDeskewInfo (imageProjection.cpp:395-491); returns the number of samples to pop. */
+  static int64_t odomDeskewInfo(const std::vector<fbr_odom_sample>& queue, double timeScanCur, double timeScanNext,
+                                fbr_odom_info& out) {
+    int64_t n_pop = 0;
+    check(fbr_odom_deskew_info(queue.data(), (int64_t)queue.size(), timeScanCur, timeScanNext, &out, &n_pop),
+          "fbr_odom_deskew_info");
+    return n_pop;
+  }
+  /* Constant velocity from the last two registration results, for hosts without odometry. */
+  static void motionFromPoses(const float prev[6], const float cur[6], double dt, double scanPeriod, double dtNext,
+                              fbr_motion& out, float guessOut[6]) {
+    check(fbr_motion_from_poses(prev, cur, dt, scanPeriod, dtNext, &out, guessOut), "fbr_motion_from_poses");
+  }
+  /* updateInitialGuess (mapOptmization.h:799-855) on a caller-owned state. */
+  static void updateInitialGuess(fbr_guess_state& state, const fbr_odom_info* odom, const fbr_deskew_table* table,
+                                 bool haveKeyframes, bool useImuHeading, float pose[6]) {
+    check(fbr_update_initial_guess(&state, odom, table, haveKeyframes ? 1 : 0, useImuHeading ? 1 : 0, pose),
+          "fbr_update_initial_guess");
+  }
+
  private:
   Context& c_;
   std::deque<PointCloud2> cloudQueue_;
