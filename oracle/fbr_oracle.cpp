@@ -1405,8 +1405,9 @@ int orc_register(const fbr_params* P, void* map, const fbr_point_xyzi* corner, i
 }
 
 // cloudHandler minus the ROS queue: projection, features, registration with the time gate.
+// no_crop: the map is a keyframe local map, registered whole as in orc_register.
 int orc_process_scan(void* s, void* map, const fbr_point_xyzirt* pts, int64_t n_in, double stamp, float pose[6],
-                     fbr_reg_stats* st, int nthreads) {
+                     fbr_reg_stats* st, int nthreads, int no_crop) {
   orc_stream* S = (orc_stream*)s;
   StageTimer tm(0);
   Projection pr;
@@ -1420,7 +1421,7 @@ int orc_process_scan(void* s, void* map, const fbr_point_xyzirt* pts, int64_t n_
   if (stamp - S->timeLastProcessing >= S->P.mapping_process_interval) {
     S->timeLastProcessing = stamp;
     registration_core(S->P, *(Map*)map, F.corner.data(), (int64_t)F.corner.size(), F.surf.data(),
-                      (int64_t)F.surf.size(), pose, R, nthreads, S->table(), false, &S->isDegenerate);
+                      (int64_t)F.surf.size(), pose, R, nthreads, S->table(), no_crop != 0, &S->isDegenerate);
   } else {
     R.st.status = FBR_REG_SKIPPED_INTERVAL;
   }

@@ -59,7 +59,7 @@ def lib():
         L.orc_map_create_raw.argtypes = [_VP, _I64, _VP, _I64]
         L.orc_kf_extract.argtypes = [_VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_double, _VP, _VP,
                                      _VP, _VP, _VP]
-        L.orc_process_scan.argtypes = [_VP, _VP, _VP, _I64, ctypes.c_double, _VP, _VP, ctypes.c_int]
+        L.orc_process_scan.argtypes = [_VP, _VP, _VP, _I64, ctypes.c_double, _VP, _VP, ctypes.c_int, ctypes.c_int]
         L.orc_affine_from_pose.argtypes = [_VP, _VP]
         L.orc_pose_from_affine.argtypes = [_VP, _VP]
         L.orc_jacobi.argtypes = [_VP, ctypes.c_int, _VP, _VP]
@@ -129,10 +129,12 @@ class Stream:
                     surf=surf[:ns.value].copy(), n_points=npnt.value)
 
     def process_scan(self, omap, pts, stamp, pose, n_threads=4):
+        """cloudHandler on one scan; a keyframe local map (Map(raw=True)) is registered whole, as
+        Map.register does."""
         pose = np.ascontiguousarray(pose, dtype=np.float32).copy()
         st = FbrRegStats()
         lib().orc_process_scan(self.h, omap.h, ptr(pts), len(pts), ctypes.c_double(stamp),
-                               ptr(pose), ctypes.byref(st), n_threads)
+                               ptr(pose), ctypes.byref(st), n_threads, int(omap.no_crop))
         return pose, st.as_dict()
 
     def __del__(self):
