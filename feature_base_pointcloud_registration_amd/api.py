@@ -17,7 +17,7 @@ import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, GUESS_STATE, IMU_SAMPLE, MOTION, ODOM_INFO, ODOM_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
                         FbrGmapResult, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
-                        POSE_SCORE, PointCloud2, default_params, gmap_params, icp_params, loop_params,
+                        POSE_SCORE, REG_INFO, PointCloud2, default_params, gmap_params, icp_params, info_params, loop_params,
                         pg_marginal_params, pg_params, pose_lattice, ptr, sc_params, score_params)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "fbr_gmap_params_default", "fbr_global_map_build", "fbr_global_map_get", "fbr_global_map_install",
     "fbr_global_map_save", "fbr_pcd_write_poses_ascii", "fbr_selftest_voxel_wide",
     "fbr_score_params_default", "fbr_score_poses", "fbr_pose_search",
+    "fbr_info_params_default", "fbr_reg_info_poses", "fbr_batch_info", "fbr_reg_info_variances",
     "fbr_comm_unique_id", "fbr_comm_create", "fbr_comm_create_local", "fbr_comm_destroy", "fbr_batch_allgather",
 ]
 
@@ -176,6 +177,10 @@ def lib():
             "fbr_selftest_voxel_wide": (ctypes.c_int, [_VP, _VP, _I64, ctypes.c_float, _VP, _VP]),
             "fbr_score_params_default": (None, [_VP]),
             "fbr_score_poses": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP]),
+            "fbr_info_params_default": (None, [_VP]),
+            "fbr_reg_info_poses": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP]),
+            "fbr_batch_info": (ctypes.c_int, [_VP, _VP, _VP]),
+            "fbr_reg_info_variances": (ctypes.c_int, [_VP, _VP, _VP]),
             "fbr_pose_search": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _VP]),
             "fbr_comm_unique_id": (ctypes.c_int, [_VP]),
             "fbr_comm_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
@@ -377,6 +382,16 @@ def affine_from_pose(pose):
     m = np.zeros(16, np.float32)
     lib().fbr_affine_from_pose(ptr(np.ascontiguousarray(pose, np.float32)), ptr(m))
     return m.reshape(4, 4)
+
+
+def reg_info_variances(info, floor=None):
+    """The between-factor variances of one REG_INFO record: max(var_tangent[k], floor[k]) in the order
+    Context.pg_add_between_poses takes (fbr_reg_info_variances; floor None: no floor)."""
+    rec = np.ascontiguousarray(np.asarray(info, REG_INFO).reshape(-1)[:1])
+    fl = None if floor is None else np.ascontiguousarray(floor, np.float64).reshape(6)
+    out = np.zeros(6, np.float64)
+    _check(lib().fbr_reg_info_variances(ptr(rec), None if fl is None else ptr(fl), ptr(out)), "fbr_reg_info_variances")
+    return out
 
 
 def pose_from_affine(m):
@@ -970,6 +985,36 @@ class Context:
                                      ctypes.byref(n)), "fbr_pose_search")
         return poses[:n.value].copy(), sc[:n.value].copy(), idx[:n.value].copy()
 
+    # ---- registration information (include/fbr.h "registration information") ----
+    def reg_info(self, corner, surf, poses, **params):
+        """How well the map determines each pose [roll, pitch, yaw, x, y, z] of a scan-frame cloud
+        (corner, surf: the mapping-leaf down-samples): a REG_INFO record array [n_poses] with the
+        Gauss-Newton normal matrix H at the pose, its spectrum (eig, evec, rank) and the covariance in
+        the pose's own increments (cov) and in the pose graph's chart (cov_tangent, var_tangent).
+        params: the fields of fbr_info_params (eig_floor, unobserved_variance, sigma2, pose_chunk)."""
+        ip = info_params(**params)
+        corner = _as_points(corner, POINT_XYZI)
+        surf = _as_points(surf, POINT_XYZI)
+        poses = np.ascontiguousarray(poses, np.float32).reshape(-1, 6)
+        out = np.zeros(max(len(poses), 1), REG_INFO)
+        _check(lib().fbr_reg_info_poses(self._h, ctypes.byref(ip), ptr(corner) if len(corner) else None, len(corner),
+                                        ptr(surf) if len(surf) else None, len(surf), ptr(poses) if len(poses) else None,
+                                        len(poses), ptr(out)), "fbr_reg_info_poses")
+        return out[:len(poses)]
+
+    def batch_info(self, **params):
+        """The REG_INFO record of every job of the latest batch launch, at the job's result pose over
+        the launch's down-sampled clouds; a job that did not register has flags FBR_INFO_NOT_REGISTERED."""
+        ip = info_params(**params)
+        # the library writes one record per job of the launched batch and takes no capacity: room for
+        # the context's max_batch, whatever this object believes was staged
+        n = getattr(self, "_staged", None)
+        if n is None:
+            raise FbrError(-7, "batch_info: no batch was staged or processed through this object")
+        out = np.zeros(max(int(self.params.max_batch), n, 1), REG_INFO)
+        _check(lib().fbr_batch_info(self._h, ctypes.byref(ip), ptr(out)), "fbr_batch_info")
+        return out[:n].copy()
+
     def relocalize_search(self, points, seeds=None, k=4, sc=None, lattice=None, top=3, score=None):
         """Find the pose of one raw scan (POINT_XYZIRT) from coarse seeds: project, extract features,
         down-sample them at the two mapping leaves, take the seed poses from the argument ([n, 6]) or
@@ -1020,6 +1065,9 @@ class Context:
         stats = np.zeros(len(keep), REG_STATS)
         _check(lib().fbr_process_batch(self._h, arr, ptr(n_in), len(keep), ptr(poses), ptr(stats)),
                "fbr_process_batch")
+        # fbr_process_batch runs max_batch jobs at a time and leaves the last of those batches staged
+        mb = max(int(self.params.max_batch), 1)
+        self._staged = len(keep) - ((len(keep) - 1) // mb) * mb if len(keep) else 0
         return poses, stats
 
     def map_grid_info(self):
@@ -1231,5 +1279,5 @@ class Comm:
 
 __all__ = ["Context", "Comm", "comm_unique_id", "FbrError", "FbrParams", "default_params", "lib", "device_count",
            "affine_from_pose", "pose_from_affine", "pcd_read", "pcd_write", "pcd_write_poses", "msg_to_points", "points_to_msg", "PointCloud2",
-           "imu_convert", "imu_deskew_info",
+           "imu_convert", "imu_deskew_info", "reg_info_variances",
            "EXPORTED_SYMBOLS"]

@@ -20,9 +20,9 @@ OBJ = os.path.join(HERE, "build")
 HIP_SOURCES = ["k_project.hip", "k_features.hip", "k_voxel.hip", "k_voxel_ring.hip", "k_voxel_large.hip", "k_concat.hip",
                "k_register.hip", "k_knn_r1.hip", "k_knn_r1f.hip",
                "k_knn_r2.hip", "k_knn_r2f.hip", "k_knn_r4.hip", "k_knn_r4f.hip", "k_knn_tile.hip", "k_keyframe.hip", "k_grid.hip",
-               "k_icp.hip", "k_scancontext.hip", "k_posegraph.hip", "k_pg_marginals.hip", "k_pg_direct.hip", "k_gmap.hip", "k_score.hip", "k_selftest.hip", "fbr_api.hip", "fbr_stages.hip",
+               "k_icp.hip", "k_scancontext.hip", "k_posegraph.hip", "k_pg_marginals.hip", "k_pg_direct.hip", "k_gmap.hip", "k_score.hip", "k_reg_info.hip", "k_selftest.hip", "fbr_api.hip", "fbr_stages.hip",
                "fbr_scan.hip", "fbr_batch.hip", "fbr_comm.hip", "fbr_map.hip", "fbr_loop.hip", "fbr_sc.hip", "fbr_pg.hip",
-               "fbr_gmap.hip", "fbr_score.hip"]
+               "fbr_gmap.hip", "fbr_score.hip", "fbr_reg_info.hip"]
 HOST_SOURCES = ["fbr_pcd.cpp", "fbr_msg.cpp", "fbr_imu.cpp", "fbr_odom.cpp"]  # host-only C++ in the same library (PCD, PointCloud2, IMU, odometry / motion)
 ARCH = os.environ.get("FBR_OFFLOAD_ARCH", "gfx950")
 

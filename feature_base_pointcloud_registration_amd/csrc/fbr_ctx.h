@@ -12,6 +12,7 @@
 //   fbr_pg.hip      pose graph: the factor list, the Levenberg-Marquardt driver, correctPoses
 //   fbr_gmap.hip    global map: build from the keyframe store, get, install, save
 //   fbr_score.hip   pose scoring: a scan against the map at many poses, the lattice search
+//   fbr_reg_info.hip  registration information: the normal matrix and covariance of poses and batch jobs
 //
 // and the headers free of HIP, each checked on a CPU by a program under tests/native:
 //   fbr_knobs.h     the environment knobs
@@ -530,6 +531,14 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   GrowDev<ScorePartial> d_score_partial;      // [chunk][work items of a pose]
   GrowDev<fbr_pose_score> d_score_out;        // [chunk]
   GrowDev<unsigned long long> d_score_keys;   // [chunk][n_corner + n_surf], calls that ask for the keys
+
+  // ---- registration information (fbr_reg_info.hip) ----
+  // Scratch of fbr_reg_info_poses / fbr_batch_info, grown on demand and sized by the poses (jobs) of
+  // one launch (fbr_info_params.pose_chunk); nothing else reads or writes it.
+  GrowDev<float4> d_info_cloud;       // fbr_reg_info_poses: the clouds, corner then surf
+  GrowDev<float> d_info_pose;         // [chunk][6]
+  GrowDev<double> d_info_partial;     // [chunk][work items of a job][kInfoPartial]
+  GrowDev<fbr_reg_info> d_info_out;   // [chunk]
 
   // ---- profiling (fbr_api.hip; the timers stand with the events above) ----
   bool profiling = false;

@@ -558,6 +558,30 @@ struct ScoreArgs {
 void launch_score_nn(hipStream_t s, const ScoreArgs& a);
 void launch_score_sum(hipStream_t s, const ScoreArgs& a);
 
+// ---- registration information (k_reg_info.hip; the record's arithmetic is fbr_reg_info.h's) ----
+constexpr int kInfoPartial = 32;  // doubles per item partial: 21 H upper + 6 g + row count + rss, 3 zero pads
+struct InfoArgs {
+  const float4* corner;         // job j's corner points at corner + j * stride_c (stride 0: one cloud for every pose)
+  const float4* surf;
+  int64_t stride_c, stride_s;
+  const int32_t* ncnt;          // [n_jobs] per-job point counts, or null: nc / ns for every job
+  const int32_t* nscnt;
+  int32_t nc, ns;               // with per-job counts: their cap (a job's points never pass its stride)
+  int32_t n_jobs;               // jobs (poses) of this launch
+  int32_t ipc, ipp;             // work items of a job's corner points / of all its points (from the largest job)
+  const float* poses;           // [n_jobs][6]
+  const fbr_reg_stats* stats;   // [n_jobs] or null: a job whose status is not FBR_REG_OK did not register
+  const int32_t* err;           // [n_jobs] or null: nor did a job with a feature capacity error
+  MapGrid mc, ms;
+  float crop_half[3];
+  int32_t nocrop;               // 1: keyframe local map
+  double eig_floor, unobserved, sigma2;
+  double* partial;              // [n_jobs][ipp][kInfoPartial]
+  fbr_reg_info* out;            // [n_jobs]
+};
+void launch_reg_info_items(hipStream_t s, const InfoArgs& a);
+void launch_reg_info_jobs(hipStream_t s, const InfoArgs& a);
+
 // ---- pose graph (k_posegraph.hip; the arithmetic is fbr_pg.h's) ----
 struct PgState {
   double cost[2];      // F of the linearised poses / of the trial poses

@@ -270,6 +270,35 @@ def pose_lattice(half=(0.0, 0.0, 0.0, 0.0), step=(0.0, 0.0, 0.0, 0.0)):
     return FbrPoseLattice((ctypes.c_float * 4)(*half), (ctypes.c_float * 4)(*step))
 
 
+# registration information (include/fbr.h "registration information")
+FBR_INFO_NO_ROWS = 1
+FBR_INFO_FEW_ROWS = 2
+FBR_INFO_BAD_POSE = 4
+FBR_INFO_NOT_REGISTERED = 8
+
+
+class FbrInfoParams(_Dictable):
+    _fields_ = [("eig_floor", ctypes.c_double), ("unobserved_variance", ctypes.c_double), ("sigma2", ctypes.c_double),
+                ("pose_chunk", ctypes.c_int32), ("reserved_", ctypes.c_int32 * 5)]
+
+
+# fbr_reg_info as a record array: one per pose or batch job
+REG_INFO = np.dtype([("H", np.float64, (6, 6)), ("g", np.float64, 6), ("rss", np.float64), ("sigma2", np.float64),
+                     ("eig", np.float64, 6), ("evec", np.float64, (6, 6)), ("cov", np.float64, (6, 6)),
+                     ("cov_tangent", np.float64, (6, 6)), ("var_tangent", np.float64, 6), ("n_rows", np.int32, 2),
+                     ("n_query", np.int32, 2), ("rank", np.int32), ("flags", np.int32)])
+assert REG_INFO.itemsize == 1336
+
+
+def info_params(**kw):
+    """fbr_info_params_default: eigenvalue floor 100, unobserved variance 1e4 ("unknown"), sigma2 from the
+    residuals (0), pose_chunk 0 (1024 poses or jobs per launch)."""
+    p = FbrInfoParams(100.0, 1e4, 0.0, 0)
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
 FBR_OK = 0
 FBR_REG_OK = 0
 FBR_REG_NOT_ENOUGH_FEATURES = 1

@@ -682,6 +682,114 @@ int fbr_pose_search(fbr_ctx* ctx, const fbr_score_params* sp, const fbr_point_xy
                     const fbr_pose_lattice* lattice, int64_t top_k, float* poses_out, fbr_pose_score* scores_out,
                     int64_t* index_out, int64_t* n_out);
 
+/* ---- registration information: Hessian and covariance of a registered pose ----------
+ * fbr_score_poses says how well a scan fits the map at a pose; this says how well the map determines
+ * the pose, and in which directions: the Gauss-Newton normal matrix at the pose, its spectrum, and a
+ * covariance in the pose graph's chart, so that fbr_pg_add_between_poses can be given variances that
+ * know a corridor from a crossing.  fbr_reg_stats.degenerate (one bit, iteration 0, one threshold)
+ * stays what it is.
+ *
+ * Inputs: a pose p = [roll, pitch, yaw, x, y, z] (float) and corner and surf clouds taken as given,
+ * in the scan frame (callers pass the mapping-leaf down-samples, as for fbr_score_poses).  The map is
+ * the current registration map; an installed map is cropped by registration's inclusive box
+ * [(-h) + t, h + t] (float, h = fbr_params.crop_half, t = p's translation), a keyframe local map is
+ * not cropped, as in fbr_register.
+ *
+ * One pass of cornerOptimization / surfOptimization runs at p exactly as the Gauss-Newton residual
+ * pass runs it:
+ *   T, trig = pcl::getTransformation of p in float (glibc sinf / cosf), q = T s as
+ *   pointAssociateToMap writes it for each scan point s (float, ((T0 sx + T1 sy) + T2 sz) + T3);
+ *   the 5 nearest map points of q (corner points in the corner map, surf points in the surf map) by
+ *   (d2, map index), d2 in flann::L2_Simple's float order, kept iff d2[4] < 1;
+ *   the line fit and its eigenvalue gate (D1[0] > 3 D1[1]) or the plane fit and its 0.2 m gate, then
+ *   the residual with s = 1 - 0.9 |d| (corner) or 1 - 0.9 |d| / sqrt(|q|) (surf), kept iff s > 0.1;
+ *   the row a = [d/droll, d/dpitch, d/dyaw, c.x, c.y, c.z] and b = -c.intensity, as float32
+ *   (LMOptimization, mapOptmization.h:1286-1332).
+ * No fit cache and no reuse flag: every query is fitted from its current neighbours.
+ *
+ * From the accepted rows, in double (a float x float product is exact in double):
+ *   H = sum a a^T (the 21 upper entries summed, stored as a full symmetric row-major [36]),
+ *   g = sum a b, rss = sum b b; n_rows[2] the accepted rows and n_query[2] the points, corner then surf;
+ *   n = n_rows[0] + n_rows[1];  sigma2 = rss / max(n - 6, 1), replaced by params.sigma2 when that is > 0;
+ *   eig[6] ascending and evec[36] (row i = the unit eigenvector of eig[i]) by a cyclic Jacobi of H in
+ *   double (csrc/fbr_reg_info.h: at most 16 sweeps of the 15 rotations (0,1), (0,2) .. (4,5); rotation
+ *   t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)), theta = (a_qq - a_pp) / (2 a_pq); equal
+ *   eigenvalues keep their order of appearance on the diagonal; a sweep that finds every
+ *   off-diagonal entry zero ends it; from the fifth sweep on an entry with |a_pp| + 100 |a_pq| == |a_pp|
+ *   and |a_qq| + 100 |a_pq| == |a_qq| is set to zero without a rotation);
+ *   rank = the number of eig[i] > params.eig_floor (default 100, the reference's degeneracy
+ *   threshold, :1359);
+ *   cov = sum_i v_i v_i^T w_i,  w_i = sigma2 / eig[i] when eig[i] > eig_floor, otherwise
+ *   params.unobserved_variance.  Its default, 1e4, means "unknown": a direction the scan does not
+ *   constrain gets a variance no consumer can mistake for a measurement.  (A pseudo-inverse would
+ *   report zero variance in exactly that direction, so it is not used.)
+ *   cov_tangent = S cov S^T, var_tangent = diag(cov_tangent): S = blockdiag(E, R^T) maps a pose
+ *   increment [droll, dpitch, dyaw, dx, dy, dz] to the pose graph's chart T (+) [w; v] =
+ *   (R Exp(w), t + R v) (below, "Chart"), R = Rz(yaw) Ry(pitch) Rx(roll),
+ *   E = [[1, 0, -sin pitch], [0, cos roll, sin roll cos pitch], [0, -sin roll, cos roll cos pitch]],
+ *   both in double from the float pose.  var_tangent is in the order fbr_pg_add_between_poses takes.
+ *   flags: FBR_INFO_NO_ROWS (n = 0), FBR_INFO_FEW_ROWS (0 < n < 6), FBR_INFO_BAD_POSE (a non-finite
+ *   pose component), FBR_INFO_NOT_REGISTERED (fbr_batch_info: the job did not register).  A flagged
+ *   record has H = g = 0, rss = sigma2 = 0, eig = 0, evec = I, rank = 0 and cov = cov_tangent =
+ *   unobserved_variance I; n_query and n_rows are still the counts of the pass (0 where no pass ran).
+ * eig_floor, unobserved_variance not finite or not > 0, sigma2 negative or not finite, a negative
+ * pose_chunk: FBR_ERR_INVALID_ARG.
+ *
+ * A record's bytes depend on the pose, the clouds and the map alone: not on the other poses of a
+ * call, the other jobs of a batch, pose_chunk or the run (one partial per block of 256 queries with
+ * a fixed summation tree, a job's partials added in order, no float or double atomics).  Nor do they
+ * depend on the order of a cloud's points: each cloud is summed in canonical order, its points sorted
+ * ascending by the bit patterns of (x, y, z, intensity) read as unsigned words, so the Morton-ordered
+ * down-sample of a batch job and fbr_voxel_grid's key-ordered one of the same features give the same
+ * record. */
+#define FBR_INFO_NO_ROWS 1
+#define FBR_INFO_FEW_ROWS 2
+#define FBR_INFO_BAD_POSE 4
+#define FBR_INFO_NOT_REGISTERED 8
+
+typedef struct fbr_info_params {
+  double eig_floor;            /* 100 */
+  double unobserved_variance;  /* 1e4: "unknown" */
+  double sigma2;               /* 0: from the residuals */
+  int32_t pose_chunk;          /* poses (jobs) per launch; 0 = 1024 */
+  int32_t reserved_[5];
+} fbr_info_params;
+
+typedef struct fbr_reg_info {
+  double H[36];
+  double g[6];
+  double rss, sigma2;
+  double eig[6];
+  double evec[36];
+  double cov[36];
+  double cov_tangent[36];
+  double var_tangent[6];
+  int32_t n_rows[2];   /* corner, surf rows accepted */
+  int32_t n_query[2];  /* corner, surf points */
+  int32_t rank;
+  int32_t flags;       /* FBR_INFO_* */
+} fbr_reg_info;
+
+void fbr_info_params_default(fbr_info_params* p);
+/* out [n_poses]; poses [n_poses][6].  Poses are processed pose_chunk at a time on scratch of the
+ * call's own, so the context's memory does not grow with n_poses.  Changes neither the map, the
+ * stream state, a staged batch nor what fbr_diag_knn_last / fbr_diag_gn_last return.  Null or
+ * negative arguments: FBR_ERR_INVALID_ARG; no map: FBR_ERR_STATE; n_poses = 0 succeeds and writes
+ * nothing.  A non-finite pose is not an error: its record is flagged. */
+int fbr_reg_info_poses(fbr_ctx* ctx, const fbr_info_params* ip, const fbr_point_xyzi* corner, int64_t n_corner,
+                       const fbr_point_xyzi* surf, int64_t n_surf, const float* poses, int64_t n_poses,
+                       fbr_reg_info* out);
+/* The same pass for every job of the latest batch launch, over that launch's down-sampled clouds at
+ * each job's result pose (what fbr_batch_results returns): out [n_jobs].  Waits for the launches in
+ * flight, as fbr_batch_labels; alters nothing of the launch chain or its results.  A job that did not
+ * register (FBR_REG_NOT_ENOUGH_FEATURES, FBR_REG_FEATURE_CAPACITY) gets a flagged record
+ * (FBR_INFO_NOT_REGISTERED).  FBR_ERR_STATE before any launch and after a single-scan call has
+ * dropped the batch. */
+int fbr_batch_info(fbr_ctx* ctx, const fbr_info_params* ip, fbr_reg_info* out /* [n_jobs] */);
+/* variances_out[k] = max(info->var_tangent[k], floor[k]) (floor may be NULL: no floor), the noise
+ * input of fbr_pg_add_between_poses.  Host only. */
+int fbr_reg_info_variances(const fbr_reg_info* info, const double floor[6], double variances_out[6]);
+
 /* ---- pose graph: key poses from odometry, loop and GPS factors ----------------------
  * The reference's addOdomFactor (:1517-1541), addGPSFactor (:1543-1634), the loop BetweenFactor
  * (:743-758) and correctPoses (:1735-1770), as a batch optimiser over the keyframe store, so that

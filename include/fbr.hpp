@@ -20,6 +20,7 @@
 #ifndef FBR_HPP_
 #define FBR_HPP_
 
+#include <array>
 #include <cstdint>
 #include <cstdlib>
 #include <deque>
@@ -399,6 +400,33 @@ class MapOptimization {
                           poses.data(), n, out.data(), nn_keys ? nn_keys->data() : nullptr),
           "fbr_score_poses");
     return out;
+  }
+  /* Registration information (include/fbr.h, "registration information"): the Gauss-Newton normal
+   * matrix of the features at each of n poses, its spectrum and the covariance in the pose graph's
+   * chart; batchInfo() the same for every job of the latest batch launch (n_jobs as staged), and
+   * infoVariances() the between-factor variances of one record, floored. */
+  std::vector<fbr_reg_info> regInfo(const fbr_info_params& ip, const std::vector<fbr_point_xyzi>& corner,
+                                    const std::vector<fbr_point_xyzi>& surf, const std::vector<float>& poses) {
+    const int64_t n = (int64_t)poses.size() / 6;
+    std::vector<fbr_reg_info> out((size_t)n);
+    check(fbr_reg_info_poses(c_.get(), &ip, corner.data(), (int64_t)corner.size(), surf.data(), (int64_t)surf.size(),
+                             poses.data(), n, out.data()),
+          "fbr_reg_info_poses");
+    return out;
+  }
+  std::vector<fbr_reg_info> batchInfo(const fbr_info_params& ip, int n_jobs) {
+    // fbr_batch_info writes one record per job of the launched batch and takes no capacity: room for
+    // the context's max_batch, then the caller's n_jobs (the count it staged) are returned
+    const int cap = c_.params().max_batch > n_jobs ? c_.params().max_batch : n_jobs;
+    std::vector<fbr_reg_info> out((size_t)(cap > 0 ? cap : 1));
+    check(fbr_batch_info(c_.get(), &ip, out.data()), "fbr_batch_info");
+    out.resize((size_t)(n_jobs > 0 ? n_jobs : 0));
+    return out;
+  }
+  static std::array<double, 6> infoVariances(const fbr_reg_info& info, const double* floor6 = nullptr) {
+    std::array<double, 6> v{};
+    check(fbr_reg_info_variances(&info, floor6, v.data()), "fbr_reg_info_variances");
+    return v;
   }
   struct PoseHypothesis {
     float pose[6];
