@@ -16,7 +16,7 @@ import os
 import numpy as np
 
 from .fbr_types import (DESKEW_TABLE, GUESS_STATE, IMU_SAMPLE, MOTION, ODOM_INFO, ODOM_SAMPLE, KEYPOSE, PF_FLOAT32, POINT_XYZI, POINT_XYZIRT, REG_STATS, FbrIcpResult,
-                        FbrGmapResult, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
+                        FbrGmapResult, FbrLoopPair, FbrLoopResult, FbrParams, FbrPgMarginalResult, FbrPgResult, FbrRegStats, FbrScMatch,
                         POSE_SCORE, REG_INFO, PointCloud2, default_params, gmap_params, icp_params, info_params, loop_params,
                         pg_marginal_params, pg_params, pose_lattice, ptr, sc_params, score_params)
 
@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "fbr_keyframe_params_default", "fbr_keyframes_add", "fbr_keyframes_set_pose", "fbr_keyframes_count",
     "fbr_keyframes_reset", "fbr_extract_surrounding_keyframes",
     "fbr_loop_params_default", "fbr_detect_loop_closure", "fbr_perform_loop_closure", "fbr_icp_align", "fbr_selftest_nn1",
+    "fbr_loop_candidates", "fbr_perform_loop_closures", "fbr_icp_align_batch",
     "fbr_sc_params_default", "fbr_sc_describe", "fbr_sc_update", "fbr_sc_descriptor", "fbr_sc_query",
     "fbr_sc_detect_loop_closure", "fbr_perform_loop_closure_sc",
     "fbr_pg_params_default", "fbr_pg_reset", "fbr_pg_add_prior", "fbr_pg_add_between", "fbr_pg_add_between_poses",
@@ -145,6 +146,9 @@ def lib():
             "fbr_detect_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP, _VP]),
             "fbr_perform_loop_closure": (ctypes.c_int, [_VP, ctypes.c_double, _VP, _VP]),
             "fbr_icp_align": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP]),
+            "fbr_loop_candidates": (ctypes.c_int, [_VP, _VP, _I32, _VP, _I64, _VP]),
+            "fbr_perform_loop_closures": (ctypes.c_int, [_VP, _VP, _VP, _I64, _I32, _VP]),
+            "fbr_icp_align_batch": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _I64, _VP, _I32, _VP]),
             "fbr_selftest_nn1": (ctypes.c_int, [_VP, _VP, _I64, _VP, _I64, ctypes.c_float, _VP, _VP]),
             "fbr_sc_params_default": (None, [_VP]),
             "fbr_sc_describe": (ctypes.c_int, [_VP, _VP, _VP, _I64, _VP, _I64, _VP]),
@@ -719,6 +723,66 @@ class Context:
                                    ptr(target) if len(target) else None, len(target), ctypes.byref(ip),
                                    ctypes.byref(r)), "fbr_icp_align")
         return r if raw else r.as_dict()
+
+    # ---- loop closure for many keyframe pairs ----
+    def loop_candidates(self, lparams=None, first=0):
+        """detectLoopClosure's rule for every keyframe >= first as it stood when that keyframe was the
+        last one: a list of (latest_id, closest_id), at most one per keyframe, ascending."""
+        lp = lparams if lparams is not None else loop_params()
+        n = _I64()
+        rc = lib().fbr_loop_candidates(self._h, ctypes.byref(lp), first, None, 0, ctypes.byref(n))
+        if rc != -4:  # FBR_ERR_CAPACITY: the size query's answer when there are pairs
+            _check(rc, "fbr_loop_candidates")
+        if n.value == 0:
+            return []
+        pairs = (FbrLoopPair * n.value)()
+        _check(lib().fbr_loop_candidates(self._h, ctypes.byref(lp), first, pairs, n.value, ctypes.byref(n)),
+               "fbr_loop_candidates")
+        return [(p.latest_id, p.closest_id) for p in pairs[:n.value]]
+
+    def perform_loop_closures(self, pairs, lparams=None, chunk=0, raw=False):
+        """performLoopClosure for each pair, the ICPs of a chunk in the same launches.  A pair is
+        (latest_id, closest_id), (latest_id, closest_id, pose_guess) or an FbrLoopPair.  Returns one
+        fbr_loop_result per pair (dicts; raw: FbrLoopResult structures, which pg_add_loop takes)."""
+        lp = lparams if lparams is not None else loop_params()
+        n = len(pairs)
+        arr = (FbrLoopPair * max(n, 1))()
+        for k, p in enumerate(pairs):
+            if isinstance(p, FbrLoopPair):
+                ctypes.memmove(ctypes.byref(arr[k]), ctypes.byref(p), ctypes.sizeof(FbrLoopPair))
+                continue
+            arr[k].latest_id, arr[k].closest_id = int(p[0]), int(p[1])
+            if len(p) > 2 and p[2] is not None:
+                arr[k].use_guess = 1
+                arr[k].pose_guess[:] = [float(v) for v in np.asarray(p[2], np.float32)]
+        out = (FbrLoopResult * max(n, 1))()
+        _check(lib().fbr_perform_loop_closures(self._h, ctypes.byref(lp), arr, n, chunk, out), "fbr_perform_loop_closures")
+        res = []
+        for k in range(n):  # copies: an element of `out` would keep the whole array alive
+            r = FbrLoopResult()
+            ctypes.memmove(ctypes.byref(r), ctypes.byref(out[k]), ctypes.sizeof(FbrLoopResult))
+            res.append(r if raw else r.as_dict())
+        return res
+
+    def icp_align_batch(self, sources, targets, iparams=None, chunk=0, raw=False):
+        """icp_align per (source, target) pair of host clouds, the ICPs of a chunk in the same launches."""
+        ip = iparams if iparams is not None else icp_params()
+        assert len(sources) == len(targets)
+        n = len(sources)
+        src = [_as_points(s, POINT_XYZI) for s in sources]
+        tgt = [_as_points(t, POINT_XYZI) for t in targets]
+        sp = (_VP * max(n, 1))(*[s.ctypes.data if len(s) else None for s in src])
+        tp = (_VP * max(n, 1))(*[t.ctypes.data if len(t) else None for t in tgt])
+        sn = (_I64 * max(n, 1))(*[len(s) for s in src])
+        tn = (_I64 * max(n, 1))(*[len(t) for t in tgt])
+        out = (FbrIcpResult * max(n, 1))()
+        _check(lib().fbr_icp_align_batch(self._h, sp, sn, tp, tn, n, ctypes.byref(ip), chunk, out), "fbr_icp_align_batch")
+        res = []
+        for k in range(n):
+            r = FbrIcpResult()
+            ctypes.memmove(ctypes.byref(r), ctypes.byref(out[k]), ctypes.sizeof(FbrIcpResult))
+            res.append(r if raw else r.as_dict())
+        return res
 
     def selftest_nn1(self, target, query, max_distance):
         """The ICP correspondence search alone: (index int32 [n_query], -1 = none; d2 float32)."""

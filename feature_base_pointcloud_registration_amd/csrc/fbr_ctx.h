@@ -18,6 +18,7 @@
 //   fbr_knobs.h     the environment knobs
 //   fbr_own.h       owning handles (HostWord below builds on them)
 //   fbr_pace.h      device-paced host loops: the flag words, the flag wait, run_ahead, gn_plan
+//   fbr_loop_plan.h chunks and pool layout of loop closure for many keyframe pairs
 //
 // Everything shared lives in fbr::internal, which is hidden: the library's link exports every
 // default-visibility symbol, and none of this is part of its interface.
@@ -293,6 +294,7 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
     free_grid(grid_c);
     free_grid(grid_s);
     free_grid(icp_grid);
+    for (DevGrid& g : icp_grids) free_grid(g);
     arena_free(arena);
   }
 
@@ -468,6 +470,15 @@ struct __attribute__((visibility("hidden"))) fbr_ctx {
   HostWord<unsigned long long> icp_flag;  // the progress word k_icp_solve writes (allocated on first use)
   unsigned long long icp_gen = 0;
   DevGrid icp_grid;            // the ICP's own grid over its target
+  // many pairs per launch (fbr_perform_loop_closures, fbr_icp_align_batch): the pools of one chunk
+  // (fbr_loop_plan.h), grown on demand; the progress word and its generation are the two above
+  GrowDev<float4> d_lb_src, d_lb_x, d_lb_raw, d_lb_tgt;
+  GrowDev<unsigned long long> d_lb_key;
+  GrowDev<int32_t> d_lb_far;       // the pairs' far-query lists
+  GrowDev<double> d_lb_partial;    // [blocks of the chunk][kIcpSums]
+  GrowDev<KfSeg> d_lb_segs;
+  GrowDev<uint8_t> d_lb_meta;      // argument blocks, block table, splits; control block, states, results, queue counts
+  std::vector<DevGrid> icp_grids;  // one search grid per pair of the chunk (released by ~fbr_ctx)
 
   // ---- scan-context place recognition (fbr_sc.hip) ----
   // One descriptor per keyframe, in keyframe order, described on demand (fbr_sc_update) from the

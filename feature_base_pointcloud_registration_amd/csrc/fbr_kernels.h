@@ -511,6 +511,30 @@ void launch_icp_nn(hipStream_t s, const IcpArgs& a, int mode, int first);
 void launch_icp_far(hipStream_t s, const IcpArgs& a, int mode);
 void launch_icp_solve(hipStream_t s, const IcpArgs& a, int max_iter, double teps, double feps, unsigned long long gen);
 void launch_icp_finish(hipStream_t s, const IcpArgs& a, fbr_icp_result* out);
+// Workgroups along y of a k_icp_far launch over nt target points (the target's split).
+int icp_far_split(int64_t nt);
+// Many pairs per launch (k_icp_*_batch): every pair has its own IcpArgs over its parts of the pools,
+// its own state, queue count and result; the block table maps a workgroup to {pair, block in pair}.
+struct IcpBatchCtl {
+  int32_t running;    // pairs that have not stopped
+  int32_t ticket;     // workgroups of the current k_icp_solve_batch launch that are through
+  uint32_t launches;  // k_icp_solve_batch launches done
+  int32_t pad;
+};
+struct IcpBatch {
+  const IcpArgs* args;      // device [npairs]: the iterations' arguments
+  const IcpArgs* args_fit;  // device [npairs]: the fitness pass's (gate2 = infinity)
+  const int2* table;        // device [nblocks]
+  const int32_t* nsplit;    // device [npairs]: icp_far_split of each pair's target
+  int npairs, nblocks, max_split;
+  IcpBatchCtl* ctl;         // device
+  unsigned long long* flag; // host-mapped: (generation << 32) | solve launches done << 1 | every pair stopped
+};
+void launch_icp_init_batch(hipStream_t s, const IcpBatch& b);
+void launch_icp_nn_batch(hipStream_t s, const IcpBatch& b, int mode, int first);
+void launch_icp_far_batch(hipStream_t s, const IcpBatch& b, int mode);
+void launch_icp_solve_batch(hipStream_t s, const IcpBatch& b, int max_iter, double teps, double feps, unsigned long long gen);
+void launch_icp_finish_batch(hipStream_t s, const IcpBatch& b, fbr_icp_result* out /* device [npairs] */);
 
 // ---- scan-context place recognition (k_scancontext.hip) ----
 struct ScPools {             // the clouds a segment may lie in

@@ -305,5 +305,16 @@ inline bool ingest_nt() {
   return v;
 }
 
+// ---- knobs without an environment name ---------------------------------------------------------
+// (not in the table of DESIGN.md §6, which lists what the environment sets)
+
+// Device bytes the pairs of one chunk of fbr_perform_loop_closures / fbr_icp_align_batch may take
+// when the caller leaves the chunk to the library (chunk_pairs = 0; fbr_loop_plan.h pair_bytes).
+// 256 MiB: about 400 pairs of the loop fixture's size (3,400 source and 5,100 target points,
+// ~0.6 MB each), whose ~4,000 query blocks fill the device several times over, and a small share
+// of its memory.  The call's chunk_pairs overrides it per call, and no result depends on either
+// (DESIGN.md §4.8), so it has no environment name.
+inline int64_t loop_batch_bytes() { return (int64_t)256 << 20; }
+
 }  // namespace knobs
 }  // namespace fbr

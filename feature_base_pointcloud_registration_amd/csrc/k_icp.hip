@@ -21,6 +21,8 @@
 // double atomics anywhere: two runs on the same input give the same bytes.
 // Once the state's `stopped` word is set, the iteration kernels the host had already enqueued
 // return at once.  The fitness pass (mode 1) runs the search on final * source without a gate.
+// The k_icp_*_batch kernels advance many pairs in the same launches over the same bodies (below,
+// "many pairs per launch"): a pair's bytes do not depend on which kernels ran it.
 #include <math.h>
 
 #include "fbr_common.h"
@@ -46,8 +48,10 @@ __device__ __forceinline__ void icp_consider(const float4 p, uint32_t id, float 
   }
 }
 
-__global__ void k_icp_init(IcpArgs a) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// The bodies below are shared by the single-pair kernels (k_icp_*: the block in the pair is
+// blockIdx.x) and the batch kernels (k_icp_*_batch: pair and block from the block table): one copy
+// of the arithmetic, so a pair gets the same bytes either way.
+__device__ __forceinline__ void icp_init_body(const IcpArgs& a) {
   IcpState* st = a.st;
   for (int k = 0; k < 12; ++k) st->T[k] = st->fin[k] = (k == 0 || k == 5 || k == 10) ? 1.0f : 0.0f;
   st->prev_mse = DBL_MAX;
@@ -55,10 +59,15 @@ __global__ void k_icp_init(IcpArgs a) {
   *a.far_cnt = 0;
 }
 
-__global__ void __launch_bounds__(256) k_icp_nn(IcpArgs a, int mode, int first) {
+__global__ void k_icp_init(IcpArgs a) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  icp_init_body(a);
+}
+
+__device__ __forceinline__ void icp_nn_body(const IcpArgs& a, int blk, int mode, int first) {
   const IcpState* st = a.st;
   if (mode == 0 && st->stopped) return;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = (int64_t)blk * 256 + threadIdx.x;
   if (i >= a.n) return;
   float4 p = (mode || first) ? a.src[i] : a.x[i];
   if (mode) p = associate(st->fin, p);
@@ -138,17 +147,21 @@ __global__ void __launch_bounds__(256) k_icp_nn(IcpArgs a, int mode, int first) 
   }
 }
 
-__global__ void __launch_bounds__(256) k_icp_far(IcpArgs a, int mode) {
+__global__ void __launch_bounds__(256) k_icp_nn(IcpArgs a, int mode, int first) { icp_nn_body(a, blockIdx.x, mode, first); }
+
+// split / nsplit: this workgroup's part of the target's tiles (every member of the workgroup gets
+// the same values: the returns below are the whole workgroup's)
+__device__ __forceinline__ void icp_far_body(const IcpArgs& a, int blk, int split, int nsplit, int mode) {
   __shared__ float4 tile[kIcpTile];
   if (mode == 0 && a.st->stopped) return;
   const int cnt = *a.far_cnt;
-  const int q0 = blockIdx.x * 256;
+  const int q0 = blk * 256;
   if (q0 >= cnt) return;  // (the whole workgroup)
   const int qi = q0 + (int)threadIdx.x < cnt ? a.far_list[q0 + threadIdx.x] : -1;
   const float4 q = qi >= 0 ? a.x[qi] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   float best = INFINITY;
   uint32_t bi = 0xFFFFFFFFu;
-  for (int64_t t0 = (int64_t)blockIdx.y * kIcpTile; t0 < a.nt; t0 += (int64_t)gridDim.y * kIcpTile) {
+  for (int64_t t0 = (int64_t)split * kIcpTile; t0 < a.nt; t0 += (int64_t)nsplit * kIcpTile) {
     __syncthreads();
     for (int k = threadIdx.x; k < kIcpTile; k += 256) {
       float4 t = make_float4(NAN, NAN, NAN, 0.0f);  // past the end / non-finite: never a candidate
@@ -165,11 +178,15 @@ __global__ void __launch_bounds__(256) k_icp_far(IcpArgs a, int mode) {
   if (qi >= 0 && bi != 0xFFFFFFFFu) atomicMin(&a.key[qi], ((unsigned long long)__float_as_uint(best) << 32) | bi);
 }
 
-// partial[b][0..16] = count, sum s (3), sum t (3), sum t_r s_c (9), sum d2 of workgroup b's queries
-__global__ void __launch_bounds__(256) k_icp_reduce(IcpArgs a, int mode) {
+__global__ void __launch_bounds__(256) k_icp_far(IcpArgs a, int mode) {
+  icp_far_body(a, blockIdx.x, blockIdx.y, gridDim.y, mode);
+}
+
+// partial[b][0..16] = count, sum s (3), sum t (3), sum t_r s_c (9), sum d2 of block b's queries
+__device__ __forceinline__ void icp_reduce_body(const IcpArgs& a, int blk, int mode) {
   __shared__ double sh[4][kIcpSums];
   if (mode == 0 && a.st->stopped) return;
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = (int64_t)blk * 256 + threadIdx.x;
   double v[17];
 #pragma unroll
   for (int k = 0; k < 17; ++k) v[k] = 0.0;
@@ -201,9 +218,11 @@ __global__ void __launch_bounds__(256) k_icp_reduce(IcpArgs a, int mode) {
     for (int k = 0; k < 17; ++k) sh[threadIdx.x >> 6][k] = v[k];
   __syncthreads();
   if (threadIdx.x < 17)
-    a.partial[(int64_t)blockIdx.x * kIcpSums + threadIdx.x] =
+    a.partial[(int64_t)blk * kIcpSums + threadIdx.x] =
         ((sh[0][threadIdx.x] + sh[1][threadIdx.x]) + sh[2][threadIdx.x]) + sh[3][threadIdx.x];
 }
+
+__global__ void __launch_bounds__(256) k_icp_reduce(IcpArgs a, int mode) { icp_reduce_body(a, blockIdx.x, mode); }
 
 // The workgroup partials summed by one wave: lane l takes blocks l, l + 64, ... in order, then a
 // butterfly (every lane ends with the same bits).
@@ -219,15 +238,16 @@ __device__ __forceinline__ void icp_sum_partials(const double* partial, int nblk
     for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
 }
 
-__global__ void __launch_bounds__(64)
-k_icp_solve(IcpArgs a, int nblk, int max_iter, double teps, double feps, unsigned long long gen) {
+// One wave.  Returns -1 to every lane but the one that ran an iteration's solve (lane 0 of a pair
+// that had not stopped), and to that one whether the pair stopped now (1) or goes on (0).
+__device__ __forceinline__ int icp_solve_body(const IcpArgs& a, int nblk, int max_iter, double teps, double feps) {
   IcpState* st = a.st;
   const int was_stopped = st->stopped;
   if (threadIdx.x == 0) *a.far_cnt = 0;  // the next search's queue
-  if (was_stopped) return;
+  if (was_stopped) return -1;
   double v[17];
   icp_sum_partials(a.partial, nblk, v);
-  if (threadIdx.x != 0) return;
+  if (threadIdx.x != 0) return -1;
   const double n = v[0];
   st->ncorr = (int32_t)n;
   int stop = 0;
@@ -278,15 +298,23 @@ k_icp_solve(IcpArgs a, int nblk, int max_iter, double teps, double feps, unsigne
     }
   }
   st->stopped = stop;
-  if (a.flag) {
-    __threadfence_system();
-    __hip_atomic_store(a.flag, pace::pack_progress(gen, (uint32_t)st->iterations, (unsigned)stop), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-  }
+  return stop;
+}
+
+// The host's progress word (fbr_pace.h), by one lane.
+__device__ __forceinline__ void icp_publish(unsigned long long* flag, unsigned long long gen, uint32_t iters, unsigned stop) {
+  __threadfence_system();
+  __hip_atomic_store(flag, pace::pack_progress(gen, iters, stop), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__global__ void __launch_bounds__(64)
+k_icp_solve(IcpArgs a, int nblk, int max_iter, double teps, double feps, unsigned long long gen) {
+  const int stop = icp_solve_body(a, nblk, max_iter, teps, feps);
+  if (stop >= 0 && a.flag) icp_publish(a.flag, gen, (uint32_t)a.st->iterations, (unsigned)stop);
 }
 
 // After the fitness pass: getFitnessScore and the result record.
-__global__ void __launch_bounds__(64) k_icp_finish(IcpArgs a, int nblk, fbr_icp_result* out) {
+__device__ __forceinline__ void icp_finish_body(const IcpArgs& a, int nblk, fbr_icp_result* out) {
   double v[17];
   icp_sum_partials(a.partial, nblk, v);
   if (threadIdx.x != 0) return;
@@ -302,6 +330,71 @@ __global__ void __launch_bounds__(64) k_icp_finish(IcpArgs a, int nblk, fbr_icp_
   out->transform[15] = 1.0f;
 }
 
+__global__ void __launch_bounds__(64) k_icp_finish(IcpArgs a, int nblk, fbr_icp_result* out) { icp_finish_body(a, nblk, out); }
+
+// ---- many pairs per launch ------------------------------------------------------------------------
+// args[pair] is that pair's IcpArgs over its own parts of the pools; table[workgroup] = {pair, block
+// in the pair}, every pair's blocks counted from its own query 0 (fbr_loop_plan.h).  Workgroups
+// of a stopped pair return at once, as the single-pair kernels do.
+__device__ __forceinline__ int icp_pair_blocks(const IcpArgs& a) { return a.n > 0 ? (int)((a.n + 255) / 256) : 0; }
+
+__global__ void __launch_bounds__(64) k_icp_init_batch(const IcpArgs* args, int npairs, IcpBatchCtl* ctl) {
+  const int p = blockIdx.x * 64 + threadIdx.x;
+  if (p == 0) {
+    ctl->running = npairs;
+    ctl->ticket = 0;
+    ctl->launches = 0;
+  }
+  if (p < npairs) icp_init_body(args[p]);
+}
+
+__global__ void __launch_bounds__(256) k_icp_nn_batch(const IcpArgs* args, const int2* table, int mode, int first) {
+  const int2 e = table[blockIdx.x];
+  const IcpArgs a = args[e.x];
+  icp_nn_body(a, e.y, mode, first);
+}
+
+// gridDim.y is the launch's largest target split; a pair's workgroups beyond its own return.  (The
+// 64-bit atomicMin makes a pair's keys independent of how its target is split.)
+__global__ void __launch_bounds__(256) k_icp_far_batch(const IcpArgs* args, const int2* table, const int32_t* nsplit, int mode) {
+  const int2 e = table[blockIdx.x];
+  const int ns = nsplit[e.x];
+  if ((int)blockIdx.y >= ns) return;
+  const IcpArgs a = args[e.x];
+  icp_far_body(a, e.y, blockIdx.y, ns, mode);
+}
+
+__global__ void __launch_bounds__(256) k_icp_reduce_batch(const IcpArgs* args, const int2* table, int mode) {
+  const int2 e = table[blockIdx.x];
+  const IcpArgs a = args[e.x];
+  icp_reduce_body(a, e.y, mode);
+}
+
+// One wave per pair.  A pair that stops leaves the count of running pairs; the workgroup that draws
+// the launch's last ticket publishes (launches done, nobody running) to the host.  The state a
+// solve writes is read by later launches only, so the ticket orders nothing but the count.
+__global__ void __launch_bounds__(64)
+k_icp_solve_batch(const IcpArgs* args, int npairs, IcpBatchCtl* ctl, int max_iter, double teps, double feps,
+                  unsigned long long gen, unsigned long long* flag) {
+  const IcpArgs a = args[blockIdx.x];
+  const int stop = icp_solve_body(a, icp_pair_blocks(a), max_iter, teps, feps);
+  if (threadIdx.x != 0) return;
+  if (stop > 0) (void)__hip_atomic_fetch_add(&ctl->running, -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __threadfence();
+  const int ticket = __hip_atomic_fetch_add(&ctl->ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != npairs - 1) return;
+  __threadfence();
+  __hip_atomic_store(&ctl->ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the next launch's
+  const uint32_t done = ++ctl->launches;  // (the winner's alone; launches follow each other on the stream)
+  const int running = __hip_atomic_load(&ctl->running, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (flag) icp_publish(flag, gen, done, running == 0 ? 1u : 0u);
+}
+
+__global__ void __launch_bounds__(64) k_icp_finish_batch(const IcpArgs* args, fbr_icp_result* out) {
+  const IcpArgs a = args[blockIdx.x];
+  icp_finish_body(a, icp_pair_blocks(a), out + blockIdx.x);
+}
+
 inline int icp_blocks(int64_t n) { return (int)std::max<int64_t>(1, (n + 255) / 256); }
 
 }  // namespace
@@ -315,8 +408,7 @@ void launch_icp_nn(hipStream_t s, const IcpArgs& a, int mode, int first) {
 
 void launch_icp_far(hipStream_t s, const IcpArgs& a, int mode) {
   if (a.n <= 0) return;
-  const int gy = (int)std::min<int64_t>(std::max<int64_t>((a.nt + kIcpTile - 1) / kIcpTile, 1), 32);
-  fbr_launch(k_icp_far, dim3(icp_blocks(a.n), gy), dim3(256), 0, s, a, mode);
+  fbr_launch(k_icp_far, dim3(icp_blocks(a.n), icp_far_split(a.nt)), dim3(256), 0, s, a, mode);
 }
 
 void launch_icp_solve(hipStream_t s, const IcpArgs& a, int max_iter, double teps, double feps, unsigned long long gen) {
@@ -329,6 +421,32 @@ void launch_icp_finish(hipStream_t s, const IcpArgs& a, fbr_icp_result* out) {
   const int nblk = a.n > 0 ? icp_blocks(a.n) : 0;
   if (nblk) fbr_launch(k_icp_reduce, dim3(nblk), dim3(256), 0, s, a, 1);
   fbr_launch(k_icp_finish, dim3(1), dim3(64), 0, s, a, nblk, out);
+}
+
+int icp_far_split(int64_t nt) { return (int)std::min<int64_t>(std::max<int64_t>((nt + kIcpTile - 1) / kIcpTile, 1), 32); }
+
+void launch_icp_init_batch(hipStream_t s, const IcpBatch& b) {
+  fbr_launch(k_icp_init_batch, dim3((b.npairs + 63) / 64), dim3(64), 0, s, b.args, b.npairs, b.ctl);
+}
+
+void launch_icp_nn_batch(hipStream_t s, const IcpBatch& b, int mode, int first) {
+  if (b.nblocks <= 0) return;
+  fbr_launch(k_icp_nn_batch, dim3(b.nblocks), dim3(256), 0, s, mode ? b.args_fit : b.args, b.table, mode, first);
+}
+
+void launch_icp_far_batch(hipStream_t s, const IcpBatch& b, int mode) {
+  if (b.nblocks <= 0) return;
+  fbr_launch(k_icp_far_batch, dim3(b.nblocks, b.max_split), dim3(256), 0, s, mode ? b.args_fit : b.args, b.table, b.nsplit, mode);
+}
+
+void launch_icp_solve_batch(hipStream_t s, const IcpBatch& b, int max_iter, double teps, double feps, unsigned long long gen) {
+  if (b.nblocks > 0) fbr_launch(k_icp_reduce_batch, dim3(b.nblocks), dim3(256), 0, s, b.args, b.table, 0);
+  fbr_launch(k_icp_solve_batch, dim3(b.npairs), dim3(64), 0, s, b.args, b.npairs, b.ctl, max_iter, teps, feps, gen, b.flag);
+}
+
+void launch_icp_finish_batch(hipStream_t s, const IcpBatch& b, fbr_icp_result* out) {
+  if (b.nblocks > 0) fbr_launch(k_icp_reduce_batch, dim3(b.nblocks), dim3(256), 0, s, b.args_fit, b.table, 1);
+  fbr_launch(k_icp_finish_batch, dim3(b.npairs), dim3(64), 0, s, b.args_fit, out);
 }
 
 }  // namespace fbr

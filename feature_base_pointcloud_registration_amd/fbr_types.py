@@ -121,6 +121,12 @@ class FbrLoopResult(_Dictable):
                 ("between", ctypes.c_float * 16)]
 
 
+class FbrLoopPair(_Dictable):
+    """fbr_loop_pair: one entry of fbr_perform_loop_closures."""
+    _fields_ = [("latest_id", ctypes.c_int32), ("closest_id", ctypes.c_int32), ("use_guess", ctypes.c_int32),
+                ("pose_guess", ctypes.c_float * 6), ("reserved_", ctypes.c_int32)]
+
+
 def icp_params(**kw):
     """performLoopClosure's "ICP Settings" (mapOptmization.h:689-694)."""
     p = FbrIcpParams(100.0, 100, 1e-6, 1e-6)

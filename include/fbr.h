@@ -504,6 +504,43 @@ int fbr_icp_align(fbr_ctx* ctx, const fbr_point_xyzi* source, int64_t n_source, 
 int fbr_selftest_nn1(fbr_ctx* ctx, const fbr_point_xyzi* target, int64_t n_target, const fbr_point_xyzi* query,
                      int64_t n_query, float max_distance, int32_t* index, float* d2);
 
+/* ---- loop closure for many keyframe pairs (DESIGN §4.8 "many pairs") ---------------------------
+ * The calls above close one loop, for the last keyframe.  The ones below take an explicit list of
+ * pairs (to re-close a recorded session, or to re-check loops after fbr_pg_apply moved the key
+ * poses) and advance the ICP of all pairs of a chunk in the same kernel launches.  Every result is
+ * byte for byte what the single call returns for that pair; two calls return the same bytes, and
+ * so do different chunk sizes and pair orders. */
+typedef struct fbr_loop_pair {
+  int32_t latest_id, closest_id;  /* 0 <= closest_id, latest_id < keyframe count, closest_id != latest_id */
+  int32_t use_guess;              /* 1: pose_guess stands for latest_id's stored pose, exactly as
+                                     match.pose_guess does in fbr_perform_loop_closure_sc */
+  float   pose_guess[6];
+  int32_t reserved_;
+} fbr_loop_pair;
+
+/* detectLoopClosure's rule for every keyframe i >= first_keyframe in ascending order, as it stood
+ * when i was the last keyframe: the search runs over keyframes 0..i with stamp = keyframe i's time
+ * (the float d2 < r^2 test, ascending d2 with ties by index), takes the first hit with
+ * |time - stamp| > search_time_diff, and none if that hit is i itself.  At most one pair per
+ * keyframe, use_guess = 0.  Host only.  cap too small: FBR_ERR_CAPACITY with *n_pairs the needed
+ * count (pairs == NULL with cap == 0 is the size query); the first cap pairs are written. */
+int fbr_loop_candidates(fbr_ctx* ctx, const fbr_loop_params* lp, int32_t first_keyframe, fbr_loop_pair* pairs,
+                        int64_t cap, int64_t* n_pairs);
+/* out[p] is performLoopClosure for pairs[p] with latest_id as the last keyframe: the target window
+ * closest_id +- search_num is clipped to [0, latest_id]; source, target, VoxelGrid, ICP, status,
+ * pose_corrected and between as fbr_perform_loop_closure's.  With latest_id the last keyframe it is
+ * that call's result; for an earlier keyframe it is what that call returned when latest_id was the
+ * last keyframe with the same stored poses.  An invalid pair: FBR_ERR_INVALID_ARG before anything
+ * is enqueued.  n_pairs == 0: FBR_OK.  No key pose, registration map or keyframe local map is
+ * touched.  chunk_pairs: pairs in flight at once; 0 = as many as the library's device-byte budget
+ * allows (csrc/fbr_knobs.h loop_batch_bytes).  No result depends on it. */
+int fbr_perform_loop_closures(fbr_ctx* ctx, const fbr_loop_params* lp, const fbr_loop_pair* pairs, int64_t n_pairs,
+                              int32_t chunk_pairs, fbr_loop_result* out /* [n_pairs] */);
+/* fbr_icp_align per pair on host clouds, the ICPs of a chunk in the same launches. */
+int fbr_icp_align_batch(fbr_ctx* ctx, const fbr_point_xyzi* const* sources, const int64_t* n_sources,
+                        const fbr_point_xyzi* const* targets, const int64_t* n_targets, int64_t n_pairs,
+                        const fbr_icp_params* ip, int32_t chunk_pairs, fbr_icp_result* out /* [n_pairs] */);
+
 /* ---- place recognition: scan-context descriptors and search ---------------------
  * The registration path needs a pose guess near the truth, and fbr_detect_loop_closure needs the
  * last keyframe's stored pose within search_radius of the place it revisits.  The calls below find

@@ -337,6 +337,44 @@ class MapOptimization {
           "fbr_icp_align");
     return r;
   }
+  /* Loop closure for many keyframe pairs (include/fbr.h, "loop closure for many keyframe pairs"):
+   * detectLoopClosure's rule for every keyframe >= firstKeyframe as it stood when that keyframe was
+   * the last one; performLoopClosure for an explicit list of pairs, the ICPs of chunkPairs pairs
+   * (0: the library's choice) in the same launches, each result the single call's bytes; and
+   * icpAlign for many pairs of host clouds. */
+  std::vector<fbr_loop_pair> loopCandidates(const fbr_loop_params& lp, int firstKeyframe = 0) {
+    int64_t n = 0;
+    const int rc = fbr_loop_candidates(c_.get(), &lp, firstKeyframe, nullptr, 0, &n);
+    if (rc != FBR_OK && rc != FBR_ERR_CAPACITY) check(rc, "fbr_loop_candidates");
+    std::vector<fbr_loop_pair> pairs((size_t)n);
+    if (n > 0) check(fbr_loop_candidates(c_.get(), &lp, firstKeyframe, pairs.data(), n, &n), "fbr_loop_candidates");
+    return pairs;
+  }
+  std::vector<fbr_loop_result> performLoopClosures(const std::vector<fbr_loop_pair>& pairs, const fbr_loop_params& lp,
+                                                   int chunkPairs = 0) {
+    std::vector<fbr_loop_result> r(pairs.size());
+    check(fbr_perform_loop_closures(c_.get(), &lp, pairs.data(), (int64_t)pairs.size(), chunkPairs, r.data()),
+          "fbr_perform_loop_closures");
+    return r;
+  }
+  std::vector<fbr_icp_result> icpAlignBatch(const std::vector<std::vector<fbr_point_xyzi>>& sources,
+                                            const std::vector<std::vector<fbr_point_xyzi>>& targets,
+                                            const fbr_icp_params& ip, int chunkPairs = 0) {
+    if (sources.size() != targets.size()) throw Error(FBR_ERR_INVALID_ARG, "fbr_icp_align_batch");
+    std::vector<const fbr_point_xyzi*> sp, tp;
+    std::vector<int64_t> sn, tn;
+    for (size_t k = 0; k < sources.size(); ++k) {
+      sp.push_back(sources[k].data());
+      sn.push_back((int64_t)sources[k].size());
+      tp.push_back(targets[k].data());
+      tn.push_back((int64_t)targets[k].size());
+    }
+    std::vector<fbr_icp_result> r(sources.size());
+    check(fbr_icp_align_batch(c_.get(), sp.data(), sn.data(), tp.data(), tn.data(), (int64_t)sources.size(), &ip, chunkPairs,
+                              r.data()),
+          "fbr_icp_align_batch");
+    return r;
+  }
 
   /* Place recognition (include/fbr.h, "place recognition"): scan-context descriptors of the
    * keyframes and the exhaustive search over them.  scQuery takes mapping-leaf down-sampled lidar-frame
